@@ -23,7 +23,16 @@ its own N ranks as fresh child processes (the parent never touches the GPU, noth
 and exits with the worst child's return code.  On a box with fewer GPUs than ranks the children
 share the GPUs over a gloo group (a functional run of the N-rank path, flagged in the JSON).
 
-The JSON line also carries
+A plain run does only what the headline needs: set up, `--warmup` passes, `--steps` timed passes
+(`ms_per_step` = their mean), the outputs of the last timed pass written with `--dump-outputs DIR`,
+one JSON line.  `--dump-outputs DIR` writes DIR/<name>.npy: the six embedding matrices of
+encode_data (float32; a matrix above 8 MB as a fixed, seeded sample of its rows, in row order), the
+ranks and top-1 indices of i2t and t2i and their Recall@K reports (float64); with N ranks, rank 0
+writes the ranks, top-1 indices and reports the sharded pass returns.  Inputs and weights are
+seeded, so the same arguments give the same inputs on every run.
+
+With `--full` the timed passes run under the kernel timers of the two rooflines, the library is
+ISA-audited, and the JSON line also carries
   roofline      for the dominant kernel (the LDS-tiled GRU step: gru_step_chain_kernel, one launch per
                 chain of time steps, and gru_step_kernel): algorithmic FLOPs of the timed launches
                 (2*3H*I + 2*3H*H + 14H per sequence-step) / their HIP-event time,
@@ -47,9 +56,12 @@ The JSON line also carries
                 rows the same deviation moves on separable (correlated) embeddings — the ruler
                 every optional math mode is held to;
   cached_schedule_pass  the pass for a resident, unchanged split with the level-1 schedules kept
-                between passes (opt-in; the headline pass rebuilds them like the reference).
+                between passes (opt-in; the headline pass rebuilds them like the reference);
+  and fast_mode, power, train_steps, dropin_validate, leg_seconds, library.
+The options that size those legs (--fast_steps, --train_steps, --cpu_batches, ...) act with --full only.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -78,6 +90,32 @@ from bench_legs import (TRAIN_CONFIGS, cpu_baseline, dropin_validate_bench, fast
 
 def costs_sum(costs, idx):
   return float(sum(costs[i][0] for i in idx))
+
+
+DUMP_MATRIX_BYTES = 8 << 20     # per embedding matrix: six of them stay under 64 MB with the ranks
+REPORT_KEYS = ('r1', 'r5', 'r10', 'medr', 'meanr', 'sum')
+
+
+def dump_outputs(path, embs, ranks, reports, seed=0):
+  """--dump-outputs: `embs` {name: [rows, D] device tensor} as float32 (above DUMP_MATRIX_BYTES a
+  fixed, seeded sample of rows, kept in row order), `ranks` {name: host array} and `reports`
+  {name: report_from_ranks dict} as float64.  Returns the bytes written."""
+  os.makedirs(path, exist_ok=True)
+  arrays = {}
+  for name, t in embs.items():
+    rows, d = t.shape
+    cap = max(1, DUMP_MATRIX_BYTES // (4 * d))
+    if rows > cap:
+      idx = np.sort(np.random.default_rng(seed).choice(rows, cap, replace=False))
+      t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+    arrays[name] = t.detach().float().cpu().numpy()
+  for name, a in ranks.items():
+    arrays[name] = np.asarray(a, dtype=np.float64)
+  for name, rep in reports.items():
+    arrays[name] = np.array([rep[k] for k in REPORT_KEYS], dtype=np.float64)
+  for name, a in arrays.items():
+    np.save(os.path.join(path, name + '.npy'), a)
+  return sum(a.nbytes for a in arrays.values())
 
 
 def rank_environments(n, n_gpus, port, base):
@@ -137,6 +175,11 @@ def main():
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=3)
   ap.add_argument('--warmup', type=int, default=1)
+  ap.add_argument('--full', action='store_true',
+                  help='also run everything beside the headline: ISA audit of the library, the kernel timers of '
+                       'the rooflines in the timed passes, and the supplementary legs the options below size')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the outputs of the last timed pass as DIR/<name>.npy (float32 / float64)')
   ap.add_argument('--workload', default='anet_icep_val', choices=sorted(WORKLOADS))
   ap.add_argument('--rnn_type', default='attention', choices=['attention', 'maxout', 'seq2seq'])
   ap.add_argument('--embed', type=int, default=1024)
@@ -173,6 +216,12 @@ def main():
                   help='also time this many passes that reuse the level-1 schedules of a resident '
                        'split (evaluation.encode_group(plan=)); 0 = skip')
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be at least 1 and --warmup at least 0')
+  if not args.full:      # a plain run times the headline only: the legs these options size run with --full
+    for name in ('rank_check', 'cached_steps', 'fast_steps', 'power_steps', 'train_steps', 'host_steps',
+                 'api_steps', 'cpu_batches'):
+      setattr(args, name, 0)
 
   if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
     sys.exit(launch_ranks(args.gpus))
@@ -187,7 +236,7 @@ def main():
   # The ISA audit of the loaded library disassembles it in child processes (llvm-objdump, ~3 s): done
   # HERE, before this process touches the GPU — a fork of a process that holds a GPU context, and three
   # idle seconds in the middle of the run, cost the legs behind it 10 % (profiles/r06_fast_mode_ab.txt).
-  lib_info = isa_audit() if rank == 0 else None
+  lib_info = isa_audit() if rank == 0 and args.full else None
   if backend == 'gloo':
     local_rank = local_rank % max(1, torch.cuda.device_count())
   torch.cuda.set_device(local_rank)
@@ -231,12 +280,13 @@ def main():
 
   host_queue_ms = []     # per pass: host ms until the encoders / the ranking were queued
 
-  def step(plan=None, src=None):
+  def step(plan=None, src=None, keep=False):
     """One validation pass, scored: the embeddings are encoded, both directions ranked, the
     per-batch meters replayed, and the ranks brought to the host and turned into the Recall@K /
     median-rank report (evaluation.py:173-184) — all inside the timed region.  A pass does all the
     work the reference's pass does, the sort / step counts / pointer tables of its packed schedules
-    included (layers.py:94-97); only the `cached_schedule_pass` leg passes a `plan` that keeps them."""
+    included (layers.py:94-97); only the `cached_schedule_pass` leg passes a `plan` that keeps them.
+    `keep`: hold on to the pass's outputs in last['embs'] / last['ranks'] (--dump-outputs)."""
     if world == 1:
       h0 = time.perf_counter()
       cat, _, _, finish_log = encode_data_device(opt, model, batches if src is None else src,
@@ -250,6 +300,9 @@ def main():
       finish_log()     # the per-batch 'Letest' meters (evaluation.py:129), after the ranking is queued
       host = packed.cpu().numpy().astype(np.float64)     # ONE device-to-host copy for both directions
       last['rep_i'], last['rep_t'] = report_from_ranks(host[0]), report_from_ranks(host[2])
+      if keep:
+        last['embs'] = cat
+        last['ranks'] = {'i2t_ranks': host[0], 'i2t_top1': host[1], 't2i_ranks': host[2], 't2i_top1': host[3]}
       if debug:
         sys.stderr.write('pass host ms: encode queued %.1f, ranking queued %.1f, scored %.1f\n'
                          % ((h1 - h0) * 1e3, (h2 - h1) * 1e3, (time.perf_counter() - h2) * 1e3))
@@ -257,6 +310,9 @@ def main():
     res = parallel_eval.validate_sharded(opt, model, batches, device=device, dim=args.embed,
                                          assignment=assignment, timings=phase_ms, plan=plan)
     last['rep_i'], last['rep_t'] = res[0], res[1]
+    if keep:
+      last['embs'] = {}
+      last['ranks'] = {'i2t_ranks': res[2], 'i2t_top1': res[4], 't2i_ranks': res[3], 't2i_top1': res[5]}
     for k, v in phase_ms.items():
       phase_sum[k] = phase_sum.get(k, 0.0) + v
     return res[2], res[3]
@@ -267,14 +323,22 @@ def main():
       dist.barrier()
     torch.cuda.synchronize()
 
+  def kernel_timers():
+    """The HIP event pairs of the rooflines around the passes' launches (--full only)."""
+    if args.full:
+      return ops.StepTimers(), ops.SimTimers()
+    return contextlib.nullcontext(), contextlib.nullcontext()
+
   # warm-up passes run under the same timers as the timed ones: their HIP events come from (and go
   # back to) the library's free list, so the timed region creates none
   for _ in range(args.warmup):
-    with ops.StepTimers() as wt, ops.SimTimers() as wst:
+    wt, wst = kernel_timers()
+    with wt, wst:
       step()
       sync()
-    wt.collect()
-    wst.collect()
+    if args.full:
+      wt.collect()
+      wst.collect()
   sync()
   phase_sum.clear()      # the per-rank phase times below are those of the timed passes only
   if os.environ.get('CMHSE_BENCH_GC_FREEZE', '0') == '1':
@@ -284,8 +348,9 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
+  timers, sim_timers = kernel_timers()
   t0 = time.perf_counter()
-  with ops.StepTimers() as timers, ops.SimTimers() as sim_timers:
+  with timers, sim_timers:
     pass_marks = [t0]
     del host_queue_ms[:]
     gc_spans = []
@@ -296,8 +361,8 @@ def main():
         gc_spans.append(((time.perf_counter() - _t[0]) * 1e3, info.get('generation')))
     import gc as _gc
     _gc.callbacks.append(_gc_cb)
-    for _ in range(args.steps):
-      ranks_i, ranks_t = step()
+    for i in range(args.steps):
+      ranks_i, ranks_t = step(keep=args.dump_outputs is not None and i == args.steps - 1)
       pass_marks.append(time.perf_counter())   # (a pass ends with its ranks on the host)
     sync()
   elapsed = time.perf_counter() - t0
@@ -315,8 +380,8 @@ def main():
   # of a call in one launch — and gru_step_kernel): every one of its launches in the timed region
   # sits between its own HIP event pair (cmhse_timer_tiled), priced with its algorithmic FLOPs.  `all_step_kernels` adds the small-batch step kernel (the ragged
   # tails), from the event spans around each encoder call's whole step sequence.
-  spans = timers.collect()
-  sims = sim_timers.collect()
+  spans = timers.collect() if args.full else []
+  sims = sim_timers.collect() if args.full else []
   sim_ms = sum(x[0] for x in sims)
   sim_flops = sum(2.0 * x[1] * x[2] * x[3] for x in sims)
   sim_achieved = sim_flops / (sim_ms * 1e-3) / 1e12 if sim_ms > 0 else 0.0
@@ -345,8 +410,11 @@ def main():
   ms_per_step = elapsed / args.steps * 1e3
   pairs = float(N) * float(N)
 
-  clk = measured_clock_ghz()
-  traffic = measured_traffic(('gru_step_kernel<', 'gru_step_chain_kernel<'))
+  if args.dump_outputs is not None and rank == 0:
+    dump_outputs(args.dump_outputs, last.pop('embs'), last.pop('ranks'),
+                 {'i2t_report': last['rep_i'], 't2i_report': last['rep_t']})
+  last.pop('embs', None)
+
   if rank == 0:
     r1 = 100.0 * float((np.asarray(ranks_i) < 1).mean())
     out = {
@@ -385,49 +453,53 @@ def main():
         'ranks_crc32': zlib.crc32(np.asarray(ranks_i, dtype=np.int64).tobytes() +
                                   np.asarray(ranks_t, dtype=np.int64).tobytes()),
         'per_rank': per_rank,
-        'roofline': {'kernel': 'gru_step_chain_kernel / gru_step_kernel (the LDS-tiled GRU step: one launch per '
-                               'chain of time steps, or per step where a chain cannot be used)',
-                     'bound': 'mfma', 'achieved': achieved,
-                     'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                     'frac': achieved / FP32_MFMA_PEAK_TFLOPS,
-                     'traffic': traffic,
-                     'traffic_source': profile_source('r*_pmc_hbm_traffic.json'),
-                     'traffic_unit': 'fabric bytes per launch (rocprofv3 PMC FETCH_SIZE x2 + '
-                                     'WRITE_SIZE, newest profiles/r*_pmc_hbm_traffic.json)',
-                     'algorithmic_bytes_per_launch': (alg_bytes / launches) if launches else None,
-                     # north_star: achieved GB/s of the GRU = PMC traffic / live launch duration
-                     # (against ~8000 GB/s HBM; counts Infinity-Cache hits too — the kernel is
-                     # MFMA-bound, this is context)
-                     'traffic_gbps': (traffic / (ms * 1e-3 / launches) / 1e9)
-                                     if (traffic and launches and ms > 0) else None,
-                     'launches': launches,
-                     'avg_launch_us': (ms * 1e3 / launches) if launches else None,
-                     'flops_per_launch': (flops / launches) if launches else None,
-                     'kernel_time_share': (ms * 1e-3) / elapsed if elapsed > 0 else None,
-                     # context: `peak` assumes 2.4 GHz; an instrumented build of this kernel read
-                     # this in-kernel clock under load (profiles/r01_tile_trace.txt)
-                     'in_kernel_clock_ghz': clk,
-                     'in_kernel_clock_source': profile_source('r*_tile_trace.txt'),
-                     'all_step_kernels': {
-                         'achieved': flops_all / (ms_all * 1e-3) / 1e12 if ms_all > 0 else None,
-                         'launches': launches_all,
-                         'avg_launch_us': (ms_all * 1e3 / launches_all) if launches_all else None,
-                         'kernel_time_share': (ms_all * 1e-3) / elapsed if elapsed > 0 else None}},
     }
-    out['roofline_sim'] = {
-        'kernel': 'sim_kernel<Rank>', 'bound': 'mfma', 'achieved': sim_achieved,
-        'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-        'frac': sim_achieved / FP32_MFMA_PEAK_TFLOPS, 'launches': len(sims),
-        'avg_launch_us': (sim_ms * 1e3 / len(sims)) if sims else None,
-        'flops_per_launch': (sim_flops / len(sims)) if sims else None,
-        'algorithmic_bytes_per_launch': (sum(4.0 * (x[1] + x[2]) * x[3] + 8.0 * x[1] for x in sims)
-                                         / len(sims)) if sims else None,
-        'traffic': measured_traffic('sim_kernel<1'),
-        'traffic_source': profile_source('r*_pmc_hbm_traffic.json'),
-        'note': '2*nrows*M*D FLOP per direction / HIP-event time of the counting pass alone '
-                '(cmhse_sim_rank_ex timer); rank 0\'s stripe when n_gpus > 1'}
-    out['library'] = lib_info          # cmhse_version() + the ISA audit of the library this run loaded
-    leg_seconds = out['leg_seconds'] = {}
+    leg_seconds = {}
+    if args.full:
+      clk = measured_clock_ghz()
+      traffic = measured_traffic(('gru_step_kernel<', 'gru_step_chain_kernel<'))
+      out['roofline'] = {'kernel': 'gru_step_chain_kernel / gru_step_kernel (the LDS-tiled GRU step: one launch per '
+                                   'chain of time steps, or per step where a chain cannot be used)',
+                         'bound': 'mfma', 'achieved': achieved,
+                         'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                         'frac': achieved / FP32_MFMA_PEAK_TFLOPS,
+                         'traffic': traffic,
+                         'traffic_source': profile_source('r*_pmc_hbm_traffic.json'),
+                         'traffic_unit': 'fabric bytes per launch (rocprofv3 PMC FETCH_SIZE x2 + '
+                                         'WRITE_SIZE, newest profiles/r*_pmc_hbm_traffic.json)',
+                         'algorithmic_bytes_per_launch': (alg_bytes / launches) if launches else None,
+                         # north_star: achieved GB/s of the GRU = PMC traffic / live launch duration
+                         # (against ~8000 GB/s HBM; counts Infinity-Cache hits too — the kernel is
+                         # MFMA-bound, this is context)
+                         'traffic_gbps': (traffic / (ms * 1e-3 / launches) / 1e9)
+                                         if (traffic and launches and ms > 0) else None,
+                         'launches': launches,
+                         'avg_launch_us': (ms * 1e3 / launches) if launches else None,
+                         'flops_per_launch': (flops / launches) if launches else None,
+                         'kernel_time_share': (ms * 1e-3) / elapsed if elapsed > 0 else None,
+                         # context: `peak` assumes 2.4 GHz; an instrumented build of this kernel read
+                         # this in-kernel clock under load (profiles/r01_tile_trace.txt)
+                         'in_kernel_clock_ghz': clk,
+                         'in_kernel_clock_source': profile_source('r*_tile_trace.txt'),
+                         'all_step_kernels': {
+                             'achieved': flops_all / (ms_all * 1e-3) / 1e12 if ms_all > 0 else None,
+                             'launches': launches_all,
+                             'avg_launch_us': (ms_all * 1e3 / launches_all) if launches_all else None,
+                             'kernel_time_share': (ms_all * 1e-3) / elapsed if elapsed > 0 else None}}
+      out['roofline_sim'] = {
+          'kernel': 'sim_kernel<Rank>', 'bound': 'mfma', 'achieved': sim_achieved,
+          'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+          'frac': sim_achieved / FP32_MFMA_PEAK_TFLOPS, 'launches': len(sims),
+          'avg_launch_us': (sim_ms * 1e3 / len(sims)) if sims else None,
+          'flops_per_launch': (sim_flops / len(sims)) if sims else None,
+          'algorithmic_bytes_per_launch': (sum(4.0 * (x[1] + x[2]) * x[3] + 8.0 * x[1] for x in sims)
+                                           / len(sims)) if sims else None,
+          'traffic': measured_traffic('sim_kernel<1'),
+          'traffic_source': profile_source('r*_pmc_hbm_traffic.json'),
+          'note': '2*nrows*M*D FLOP per direction / HIP-event time of the counting pass alone '
+                  '(cmhse_sim_rank_ex timer); rank 0\'s stripe when n_gpus > 1'}
+      out['library'] = lib_info          # cmhse_version() + the ISA audit of the library this run loaded
+      out['leg_seconds'] = leg_seconds
 
     def leg(name, fn):
       """A supplementary leg must never cost the headline line: a failure is reported in its place."""

@@ -211,3 +211,61 @@ def test_bench_starts_its_own_ranks_and_matches_the_single_process_ranks():
   assert two['ranks_crc32'] == one['ranks_crc32']
   assert two['report_i2t_random_init'] == one['report_i2t_random_init']
   assert two['report_t2i_random_init'] == one['report_t2i_random_init']
+
+
+DUMP_NAMES = ('vid_emb', 'para_emb', 'clip_emb', 'cap_emb', 'vid_ctx', 'para_ctx',
+              'i2t_ranks', 'i2t_top1', 't2i_ranks', 't2i_top1', 'i2t_report', 't2i_report')
+
+
+def test_bench_dump_is_a_bounded_seeded_sample(tmp_path):
+  """bench.dump_outputs at the full split's sizes: a matrix above 8 MB is cut to the same seeded rows
+  on every call, kept in row order; ranks and reports are float64; all of it stays under 64 MB."""
+  import bench
+  from cmhse_amd.evaluation import report_from_ranks
+  n, sum_c, d = 4917, 17521, 1024
+  rows = {'vid_emb': n, 'para_emb': n, 'vid_ctx': n, 'para_ctx': n, 'clip_emb': sum_c, 'cap_emb': sum_c,
+          'tiny': 7}
+  # every element of a row holds the row's index, so a dumped row names the row it came from
+  embs = {k: torch.arange(r, dtype=torch.float32)[:, None].expand(r, d).contiguous() for k, r in rows.items()}
+  ranks = {'i2t_ranks': np.arange(n) % 11, 't2i_top1': np.arange(n)[::-1].copy()}
+  reports = {'i2t_report': report_from_ranks(ranks['i2t_ranks'])}
+  nbytes = bench.dump_outputs(str(tmp_path / 'a'), embs, ranks, reports)
+  bench.dump_outputs(str(tmp_path / 'b'), embs, ranks, reports)
+  assert nbytes <= 64 << 20
+  for name, r in rows.items():
+    a = np.load(str(tmp_path / 'a' / (name + '.npy')))
+    np.testing.assert_array_equal(a, np.load(str(tmp_path / 'b' / (name + '.npy'))), err_msg=name)
+    assert a.dtype == np.float32 and a.shape[1] == d and a.nbytes <= bench.DUMP_MATRIX_BYTES
+    assert a.shape[0] == min(r, bench.DUMP_MATRIX_BYTES // (4 * d)), name
+    assert (a == a[:, :1]).all() and (np.diff(a[:, 0]) > 0).all() and a[-1, 0] < r, name
+  for name, want in ranks.items():
+    a = np.load(str(tmp_path / 'a' / (name + '.npy')))
+    assert a.dtype == np.float64
+    np.testing.assert_array_equal(a, want)
+  rep = np.load(str(tmp_path / 'a' / 'i2t_report.npy'))
+  assert rep.dtype == np.float64
+  np.testing.assert_array_equal(rep, [reports['i2t_report'][k] for k in bench.REPORT_KEYS])
+
+
+@pytest.mark.gpu
+def test_plain_bench_dumps_its_last_pass_and_full_adds_the_legs(tmp_path):
+  """A plain run times --steps passes and prints the headline alone; --dump-outputs writes what its
+  last timed pass computed (the ranks are those of `ranks_crc32`).  --full adds the rooflines, the ISA
+  audit and the legs, and computes the same outputs from the same seeded inputs."""
+  import zlib
+  base = ['--gpus', '1', '--workload', 'plumbing', '--cached_steps', '0', '--power_steps', '0', '--api_steps', '0']
+  plain = _run_bench(base + ['--steps', '3', '--dump-outputs', str(tmp_path / 'plain')])
+  full = _run_bench(base + ['--full', '--dump-outputs', str(tmp_path / 'full')])
+  extra = {'roofline', 'roofline_sim', 'library', 'leg_seconds'}
+  assert plain['steps'] == 3 and plain['ms_per_step'] > 0 and not extra & set(plain)
+  assert full['steps'] == 1 and extra <= set(full)
+  assert sorted(os.listdir(str(tmp_path / 'plain'))) == sorted(n + '.npy' for n in DUMP_NAMES)
+  total = 0
+  for name in DUMP_NAMES:
+    a = np.load(str(tmp_path / 'plain' / (name + '.npy')))
+    assert a.dtype in (np.float32, np.float64), name
+    np.testing.assert_array_equal(a, np.load(str(tmp_path / 'full' / (name + '.npy'))), err_msg=name)
+    total += a.nbytes
+  assert total <= 64 << 20
+  r_i, r_t = (np.load(str(tmp_path / 'plain' / (n + '.npy'))).astype(np.int64) for n in ('i2t_ranks', 't2i_ranks'))
+  assert zlib.crc32(r_i.tobytes() + r_t.tobytes()) == plain['ranks_crc32']

@@ -7,7 +7,7 @@ mkdir -p $out
 python -m pytest tests -x -q -m gpu > $out/pytest_gpu.log 2>&1
 echo "pytest gpu rc=$?" | tee $out/summary.txt
 grep -h "passed\|failed" $out/pytest_gpu.log | tail -2 | tee -a $out/summary.txt
-python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 echo "bench rc=$?" | tee -a $out/summary.txt
 bash tools/collect_profiles.sh $R $N > $out/collect.log 2>&1
 # a rank's share of the split (8 / 4 / 2 ranks) under the whole split's plan, and the pass through the reference API

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 [ -z "$R" ] && R=$(pwd)
 D=$R/gpurun_out/$OUT
 mkdir -p $D
-B="bench.py --steps 7 --warmup 2 --cpu_batches 0 --train_steps 0 --host_steps 0 --rank_check 0 --cached_steps 0 --api_steps 0 --fast_steps 0 --power_steps 0"
+B="bench.py --full --steps 7 --warmup 2 --cpu_batches 0 --train_steps 0 --host_steps 0 --rank_check 0 --cached_steps 0 --api_steps 0 --fast_steps 0 --power_steps 0"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats -- python3 $R/$B > $D/bench_under_rocprof.json 2>/dev/null
 B2="bench.py --steps 2 --warmup 1 --cpu_batches 0 --train_steps 0 --host_steps 0 --rank_check 0 --cached_steps 0 --api_steps 0 --fast_steps 0 --power_steps 0"
