@@ -219,6 +219,12 @@ extern "C" size_t cmhse_gru_pool_workspace(int32_t S, int32_t Tmax, int64_t sum_
   return gru_ws_layout(S, sum_T, H, pool_mode, I, Tmax).total;
 }
 
+extern "C" size_t cmhse_gru_pool_workspace_tok(int32_t S, int32_t Tmax, int64_t sum_T, int32_t I,
+                                               int32_t H, int32_t pool_mode, int32_t vocab) {
+  if (sum_T <= 0 || H <= 0 || S <= 0 || I <= 0) return 0;
+  return gru_ws_layout(S, sum_T, H, pool_mode, I, Tmax, vocab).total;
+}
+
 extern "C" int cmhse_gru_pool_ws_region(int32_t S, int32_t Tmax, int64_t sum_T, int32_t I, int32_t H,
                                         int32_t pool_mode, const char* name, size_t* offset,
                                         size_t* bytes) {
@@ -314,7 +320,10 @@ int prepare_job(const cmhse_seq_batch* b, const cmhse_gru_weights* w, int32_t po
   job->w = w;
   job->out = out;
   job->kind_count = b->step_plan_host != nullptr ? b->step_plan_host : b->step_count_host;
-  job->L = gru_ws_layout(b->S, sum_T, b->H, mode_flags, b->I, b->Tmax);
+  // the token projection table when the request passes its gate AND the caller's workspace holds it
+  // (sized by cmhse_gru_pool_workspace_tok; one sized by cmhse_gru_pool_workspace runs without it)
+  job->L = gru_ws_layout(b->S, sum_T, b->H, mode_flags, b->I, b->Tmax, b->tok_rows ? b->vocab : 0);
+  if (job->L.total > workspace_bytes) job->L = gru_ws_layout(b->S, sum_T, b->H, mode_flags, b->I, b->Tmax);
   job->wsb = static_cast<char*>(workspace);
   job->sum_T = sum_T;
   job->off = 0;
@@ -367,6 +376,7 @@ int prepare_job(const cmhse_seq_batch* b, const cmhse_gru_weights* w, int32_t po
     p.gx_p0 = p0;
     p.gx_per_seq = (b->x_rows != nullptr && b->x_step_floats == 0) ? 1 : 0;
   }
+  p.tok_tab = (L.total > L.tok_tab) ? reinterpret_cast<float*>(wsb + L.tok_tab) : nullptr;
   p.w_ih_s = nullptr;
   p.w_hh_s = nullptr;
   p.xs = nullptr;
@@ -484,8 +494,37 @@ void launch_xproj(const FwdJob& j, hipStream_t stream, int64_t m_begin = 0, int6
   q.Tmax = b->Tmax;
   q.t_first = t_first;
   q.n_tiles = (q.N + 191) / 192;
+  q.vocab_rows = 0;
   const int64_t grid = static_cast<int64_t>(q.n_tiles) * ((q.rows - q.m_begin + 63) / 64);
   if (grid <= 0) return;
+  const size_t smem = TileSmem<64, 192>::kBytes;
+  hipLaunchKernelGGL(xproj_kernel, dim3(static_cast<unsigned>(grid)), dim3(kThreads), smem, stream, q);
+}
+
+// The token projection table of job j: G[v] = emb[v] W_ih^T for every token id v — the x-phase
+// accumulators a tile computes for token v (xproj_kernel has the step tile's shape and k order).
+void launch_tok_table(const FwdJob& j, hipStream_t stream) {
+  const cmhse_seq_batch* b = j.b;
+  XprojParams q;
+  q.x_rows = nullptr;
+  q.tok_rows = nullptr;
+  q.emb = b->emb_table;
+  q.step_off = nullptr;
+  q.w_ih = j.w->w_ih;
+  q.gx = const_cast<float*>(j.p.tok_tab);
+  q.p0 = 0;
+  q.rows = b->vocab;
+  q.m_begin = 0;
+  q.I = b->I;
+  q.N = 3 * b->H;
+  q.vocab = b->vocab;
+  q.x_step = 0;
+  q.Tmax = 0;
+  q.t_first = 0;
+  q.per_seq = 0;
+  q.vocab_rows = 1;
+  q.n_tiles = (q.N + 191) / 192;
+  const int64_t grid = static_cast<int64_t>(q.n_tiles) * ((q.rows + 63) / 64);
   const size_t smem = TileSmem<64, 192>::kBytes;
   hipLaunchKernelGGL(xproj_kernel, dim3(static_cast<unsigned>(grid)), dim3(kThreads), smem, stream, q);
 }
@@ -827,6 +866,25 @@ int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
     j.tail_lo = lo;
     (void)hipMemsetAsync(j.wsb + j.L.tail_sync, 0, 256, js[k]);   // the barrier counter, off the chain's path
   }
+  // Token projection tables (tok_table_rows): every step of a token-fed request reads its x phase
+  // from G, so G is queued in order in front of the request's first step (which needs it at once);
+  // requests on one stream with the same table and weights share one.  Token ids do not enter G:
+  // no upload event to wait for.
+  for (int k = 0; k < n; ++k) {
+    FwdJob& j = jobs[k];
+    if (j.p.tok_tab == nullptr) continue;
+    int m = 0;
+    for (; m < k; ++m) {
+      const FwdJob& o = jobs[m];
+      if (o.p.tok_tab != nullptr && js[m] == js[k] && o.b->emb_table == j.b->emb_table && o.b->vocab == j.b->vocab &&
+          o.w->w_ih == j.w->w_ih && o.b->I == j.b->I && o.b->H == j.b->H)
+        break;
+    }
+    if (m < k)
+      j.p.tok_tab = jobs[m].p.tok_tab;
+    else
+      launch_tok_table(j, js[k]);
+  }
   // The hoisted input projection of an inference chain's small-batch steps (x W_ih^T of the rows of
   // the steps >= t_mid) depends on the inputs only.  With a side stream it is launched THERE, now,
   // beside the tiled steps, instead of on the chain's stream when the chain reaches t_mid, where it
@@ -840,7 +898,7 @@ int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
     for (int k = 0; k < n; ++k) {
       const FwdJob& j = jobs[k];
       if (j.save || j.t_mid <= 0 || j.t_mid >= j.b->Tmax || j.b->step_events_host != nullptr ||
-          j.own_stream != nullptr)
+          j.own_stream != nullptr || j.p.tok_tab != nullptr)
         continue;
       if (!side_ready) {
         stream_after(side, main_stream);     // the caller's inputs are ready
@@ -944,6 +1002,8 @@ int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
             event_put(early_xproj[k], false);
           }
           early_xproj[k] = nullptr;
+        } else if (j.p.tok_tab != nullptr) {
+          // the small-batch steps read their gx rows from the token projection table (queued above)
         } else if (!chunked) {
           wait_uploads(stream, t + 1, j.b->Tmax);
           launch_xproj(j, stream);

@@ -209,8 +209,15 @@ __global__ __launch_bounds__(64 * NW) void gru_step_mid_kernel(const GruStepGrou
     const int o = tid + 64 * NW * q;
     const int em = m0 + (o / BU) % BM, u = u0 + (o % BU);
     const int emc = (em < p.S_t) ? em : (p.S_t - 1), uc = (u < H) ? u : (H - 1);
-    const int64_t gxrow = p.gx_per_seq ? static_cast<int64_t>(emc) : (p.off_cur + emc - p.gx_p0);
-    const float* gxr = p.gx + gxrow * 3 * H;
+    const float* gxr;
+    if (p.tok_tab != nullptr) {   // the call's token projection table: the same values as an xproj row
+      long long tok = reinterpret_cast<const long long*>(p.tok_rows[emc])[p.t];
+      tok = tok < 0 ? 0 : (tok >= p.vocab ? p.vocab - 1 : tok);
+      gxr = p.tok_tab + tok * 3 * H;
+    } else {
+      const int64_t gxrow = p.gx_per_seq ? static_cast<int64_t>(emc) : (p.off_cur + emc - p.gx_p0);
+      gxr = p.gx + gxrow * 3 * H;
+    }
     e_gx[q][0] = gxr[uc];
     e_gx[q][1] = gxr[H + uc];
     e_gx[q][2] = gxr[2 * H + uc];
@@ -478,7 +485,8 @@ __global__ __launch_bounds__(512) void gru_fwd_tail_kernel(const FwdTailParams q
 
 // Hoisted input projection of the mid-size steps: gx[m][n] = sum_k x_row(m)[k] W_ih[n][k] for the
 // packed rows p0 + m of steps >= t_first (or, for a time-constant input, for the sequences
-// themselves), 64 x 192 tiles on the shared exact-fp32 NT tile loop.
+// themselves; or, with `vocab_rows`, for token id m: the token projection table), 64 x 192 tiles
+// on the shared exact-fp32 NT tile loop.
 struct XprojParams {
   const uint64_t* x_rows;
   const uint64_t* tok_rows;
@@ -488,7 +496,7 @@ struct XprojParams {
   float* gx;
   int64_t p0, rows;      // gx row m is packed row p0 + m; this launch computes gx rows [m_begin, rows)
   int64_t m_begin;
-  int32_t I, N, vocab, x_step, Tmax, t_first, n_tiles, per_seq;
+  int32_t I, N, vocab, x_step, Tmax, t_first, n_tiles, per_seq, vocab_rows;
 };
 
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3)))
@@ -508,7 +516,7 @@ void xproj_kernel(const XprojParams p) {
     if (!av[0]) m = p.rows - 1;
     int t = 0;
     int64_t sidx = m;
-    if (!p.per_seq) {
+    if (!p.per_seq && !p.vocab_rows) {
       // packed row -> (step, sorted sequence): the last step whose first row is <= the row
       const int64_t pr = p.p0 + m;
       int lo = p.t_first, hi = p.Tmax - 1;
@@ -519,7 +527,9 @@ void xproj_kernel(const XprojParams p) {
       t = lo;
       sidx = pr - p.step_off[t];
     }
-    if (p.tok_rows != nullptr) {
+    if (p.vocab_rows) {
+      ar[0] = row_addr(p.emb + m * p.I);
+    } else if (p.tok_rows != nullptr) {
       long long tok = reinterpret_cast<const long long*>(p.tok_rows[sidx])[t];
       tok = tok < 0 ? 0 : (tok >= p.vocab ? p.vocab - 1 : tok);
       ar[0] = row_addr(p.emb + tok * p.I);

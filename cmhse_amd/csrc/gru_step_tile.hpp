@@ -35,6 +35,9 @@ struct GruStepParams {
   int64_t gx_p0;
   int32_t gx_per_seq;
   int64_t off_prev, off_cur;
+  // token projection table G[vocab, 3H] (gru_ws.hpp tok_table_rows), or NULL: the tiled steps load
+  // their x-phase accumulators and the mid-size steps their gx rows from G[clamped token]
+  const float* tok_tab;
 };
 
 // Up to kMaxJobs independent GRU chains share one launch per time step: workgroups
@@ -201,7 +204,32 @@ __device__ __forceinline__ void gru_step_tile(const GruStepParams& p, const unsi
     nt_phase_bf3_ring<BM, BNR, MSUB, 3, 4, 2>(smem, ax, bx, I, a_row0, b_row0, acc);
     if (have_h) nt_phase_bf3_ring<BM, BNR, MSUB, 3, 4, 3>(smem, ah, bh, H, a_row0, b_row0, acc);
   } else {
-    nt_phase<BM, BNR, MSUB, 3, 4, 2, VEC>(smem, ax, av, bx, bv, I, a_row0, b_row0, acc);
+    if (p.tok_tab != nullptr) {
+      // The x phase depends on the token only: its accumulators r, z, W_in x are row G[token] of
+      // the call's projection table, computed by xproj_kernel on this tile's k order (bit-identical).
+      // The row offsets of the tile's sequences go through LDS (one token lookup per row, not per
+      // accumulator register); rows past S_t read a clamped row and are never stored.
+      __shared__ int s_goff[BM];
+      if (tid < BM) {
+        const int m = m0 + tid;
+        long long tok = reinterpret_cast<const long long*>(p.tok_rows[m < S_t ? m : (S_t - 1)])[t];
+        tok = tok < 0 ? 0 : (tok >= p.vocab ? p.vocab - 1 : tok);
+        s_goff[tid] = static_cast<int>(tok) * 3 * H;
+      }
+      __syncthreads();
+      const int uc = min(u0 + wn * 32 + acc_col(lane), H - 1);
+#pragma unroll
+      for (int ms = 0; ms < MSUB; ++ms)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float* g = p.tok_tab + s_goff[a_row0 + ms * 32 + acc_row(r, lane)] + uc;
+          acc[ms][0][r] = g[0];
+          acc[ms][1][r] = g[H];
+          acc[ms][2][r] = g[2 * H];
+        }
+    } else {
+      nt_phase<BM, BNR, MSUB, 3, 4, 2, VEC>(smem, ax, av, bx, bv, I, a_row0, b_row0, acc);
+    }
     if (CHAIN) {
       // the previous step's rows of this row tile: complete (written through by their tiles)?
       if (dep.wait != nullptr && !flag_wait(dep.sync, dep.wait, dep.need)) return;

@@ -8,7 +8,9 @@
 //   v       [sumT, H]     tanh(W_lin h + b_lin) (CMHSE_POOL_ATTN)
 // with CMHSE_MATH_BF16X3: the hi/lo pre-split copies of W_ih, W_hh (and W_lin), of the input rows
 // (xs [sumT, split_ld(I)]) and of the hidden states (hs_s [sumT, split_ld(H)]);
-// and last   gx  [rows of the small-batch steps, 3H]   their hoisted input projection x W_ih^T.
+// and   gx  [rows of the small-batch steps, 3H]   their hoisted input projection x W_ih^T;
+// last, for a token-fed exact inference request that passes the gate (tok_table_rows):
+//   tok_tab [vocab, 3H]   emb W_ih^T, the x-phase accumulators of every token id (gru_ws_layout's vocab).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -41,7 +43,7 @@ constexpr int kChainMaxStepsWs = 96;   // steps one launch of gru_step_chain_ker
 constexpr int kAttBN = 256;  // columns of W_lin per attention-energy workgroup
 
 struct GruWs {
-  size_t hs, e_part, gates, argmax, v, wih_s, whh_s, wlin_s, xs, hs_s, h0_s, gx, tail_sync, chain_sync, total;
+  size_t hs, e_part, gates, argmax, v, wih_s, whh_s, wlin_s, xs, hs_s, h0_s, gx, tail_sync, chain_sync, tok_tab, total;
 };
 
 // Kernel-shape crossovers a caller may move (cmhse_tune / cmhse_ctx_tune; documented one by one in
@@ -67,7 +69,8 @@ struct GruWs {
   X(chain_min_steps, 2)       /* consecutive LDS-tiled inference steps from which they are ONE launch of gru_step_chain_kernel */ \
   X(early_xproj, 1)           /* 1: an inference call's hoisted projection starts on the side stream before the first step */ \
   X(chain_tall_min_wgs, 256)  /* 64-row workgroups per step from which a step chain uses 128-row tiles */ \
-  X(pull_waves, 32)           /* single-wave workgroups of one cmhse_pull_steps launch (host -> HBM over PCIe) */
+  X(pull_waves, 32)           /* single-wave workgroups of one cmhse_pull_steps launch (host -> HBM over PCIe) */ \
+  X(tok_table, 1)             /* 1: a token-fed exact inference call with word-steps >= 4 x vocab projects the vocabulary once */
 
 struct Tunables {
 #define CMHSE_TUNABLE_MEMBER_(name, dflt) std::atomic<int> name{dflt};
@@ -90,6 +93,20 @@ static inline int64_t gx_rows_bound(int32_t S, int32_t Tmax, int64_t sum_T) {
   return b < sum_T ? b : sum_T;
 }
 
+// Rows of the token projection table of a request (0 = none): G[v] = emb[v] W_ih^T, the x-phase
+// accumulators of token v exactly as a tile computes them (same kernel tile, same k order), so the
+// steps that read G instead of running their x phase are bit-identical.  Only for a token-fed
+// (vocab > 0), exact-fp32 inference request with dwordx4 shapes whose word-steps are at least 4 x
+// vocab (a training batch, ~3k word-steps, stays below), with tunable tok_table on; row offsets
+// v * 3H must fit an int32.
+static inline int64_t tok_table_rows(int64_t sum_T, int32_t I, int32_t H, int32_t mode_flags, int32_t vocab) {
+  if (vocab <= 0 || tunables().tok_table.load(std::memory_order_relaxed) == 0) return 0;
+  if ((mode_flags & (CMHSE_SAVE_FOR_BACKWARD | CMHSE_MATH_BF16X3)) != 0) return 0;
+  if (I % 4 != 0 || H % 4 != 0 || sum_T < 4 * static_cast<int64_t>(vocab)) return 0;
+  if (static_cast<int64_t>(vocab) * 3 * H >= (int64_t(1) << 31)) return 0;
+  return vocab;
+}
+
 constexpr int32_t kModeMask = ~(CMHSE_SAVE_FOR_BACKWARD | CMHSE_MATH_BF16X3 | CMHSE_NO_JOIN);
 
 // row length (in float units) of a bf16x3 pre-split weight row: K rounded up to whole 16-k chunks
@@ -98,7 +115,7 @@ __host__ __device__ static inline int64_t split_ld(int K) { return (static_cast<
 static inline size_t ws_align(size_t v) { return (v + 255) / 256 * 256; }
 
 static inline GruWs gru_ws_layout(int32_t S, int64_t sum_T, int32_t H, int32_t mode_flags,
-                                  int32_t I = 0, int32_t Tmax = 0) {
+                                  int32_t I = 0, int32_t Tmax = 0, int32_t vocab = 0) {
   const bool save = (mode_flags & CMHSE_SAVE_FOR_BACKWARD) != 0;
   const bool bf3 = (mode_flags & CMHSE_MATH_BF16X3) != 0;
   const int mode = mode_flags & kModeMask;
@@ -139,6 +156,8 @@ static inline GruWs gru_ws_layout(int32_t S, int64_t sum_T, int32_t H, int32_t m
   if (!save && Tmax > 0)
     off += ws_align(256 + sizeof(unsigned) * static_cast<size_t>(Tmax < kChainMaxStepsWs ? Tmax : kChainMaxStepsWs) *
                               static_cast<size_t>((S + 63) / 64));
+  L.tok_tab = off;   // the token projection table (cmhse_gru_pool_workspace_tok)
+  if (Tmax > 0) off += ws_align(static_cast<size_t>(tok_table_rows(sum_T, I, H, mode_flags, vocab)) * 3 * H * sizeof(float));
   L.total = off;
   return L;
 }

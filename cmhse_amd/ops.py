@@ -95,7 +95,7 @@ def tune(name, value=-1):
   are initialised from.  Names: tiny_max_seqs, mid_max_seqs, mid_units, mid_waves,
   tall_tile_min_wgs, mid_tall_min_seqs, bwd_mid_max_seqs, bwd_split_min_seqs, bwd_tail_min_steps,
   fwd_tail_min_steps, bwd_chunk_rows, xproj_chunk_rows, tn_rows_bm, chain_min_steps, early_xproj,
-  chain_tall_min_wgs, pull_waves, resident_timeout_ms (include/cmhse_hip.h)."""
+  chain_tall_min_wgs, pull_waves, resident_timeout_ms, tok_table (include/cmhse_hip.h)."""
   ctx = TuneContext.current()
   if ctx is not None:
     return ctx.tune(name, value)
@@ -556,7 +556,8 @@ def _prepare_fwd(weights, pool_mode, lens, I, H, device, x_ptrs=None, tok_ptrs=N
   mode_flags = pool_mode | (SAVE_FOR_BACKWARD if save_for_backward else 0)
   if math_mode() == 'bf16x3' and not save_for_backward:
     mode_flags |= MATH_BF16X3
-  ws_bytes = lib.cmhse_gru_pool_workspace(S, sched.Tmax, sched.sum_T, I, H, mode_flags)
+  vocab = emb_table.shape[0] if sched.is_tokens else 0   # (room for the token projection table)
+  ws_bytes = lib.cmhse_gru_pool_workspace_tok(S, sched.Tmax, sched.sum_T, I, H, mode_flags, vocab)
   ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
 
   w = _lib.GruWeights()

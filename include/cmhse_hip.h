@@ -142,6 +142,16 @@ typedef struct cmhse_seq_batch {
  * energy partials. */
 size_t cmhse_gru_pool_workspace(int32_t S, int32_t Tmax, int64_t sum_T, int32_t I, int32_t H,
                                 int32_t pool_mode);
+/* The same for a token-fed batch (tok_rows, emb_table of `vocab` rows): adds the token projection
+ * table G[vocab, 3H] f32 (vocab * 3H * 4 bytes: 160 MB at vocab 13 058, H 1024) when the request
+ * qualifies — inference, exact math (no CMHSE_SAVE_FOR_BACKWARD, no CMHSE_MATH_BF16X3), I and H
+ * multiples of 4, sum_T >= 4 * vocab, tunable "tok_table" on.  The call then computes G = emb W_ih^T
+ * once and its steps read their input projection from G[token] instead of multiplying
+ * x_t = emb[token] by W_ih themselves (bit-identical).  A token-fed request whose workspace was
+ * sized by cmhse_gru_pool_workspace (no room for G) runs without the table.  vocab <= 0: equal to
+ * cmhse_gru_pool_workspace. */
+size_t cmhse_gru_pool_workspace_tok(int32_t S, int32_t Tmax, int64_t sum_T, int32_t I, int32_t H,
+                                    int32_t pool_mode, int32_t vocab);
 
 /* Where a named region of that workspace lives (tests and tools that inspect what a training
  * forward kept: the gate activations, the arg-max step of the max pooling ...).  name: "hs"
@@ -501,6 +511,12 @@ int cmhse_timer_tiled(void* timer, float* ms_host, double* flops_host, double* b
  *                             (the row split into parts follows the tile count, i.e. the gradients
  *                             to fp32 rounding; profiles/r04_wgrad_rate.txt)
  *   "pull_waves"          32  single-wave workgroups of one cmhse_pull_steps launch
+ *   "tok_table"            1  a token-fed exact inference request with word-steps (sum_T) >= 4 x vocab
+ *                             projects the whole vocabulary once (G = emb W_ih^T, one launch in front
+ *                             of its first step; requests of a call with the same emb_table and W_ih
+ *                             share it) and its steps read x_t W_ih^T from G[token]; 0 = off (results
+ *                             identical).  Read when the workspace is sized
+ *                             (cmhse_gru_pool_workspace_tok) and when the call starts
  *   "multi_step_off"       0  (not a crossover, and per DEVICE rather than per context) 1 while the
  *                             multi-step kernels are switched off on the calling thread's current device
  *                             after an acknowledged timeout (cmhse_async_status below); readable, and
