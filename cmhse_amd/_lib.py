@@ -57,6 +57,7 @@ class GruBwdJob(ctypes.Structure):
 
 
 STEP_LOSS_MAX = 8       # CMHSE_STEP_LOSS_MAX
+TOPK_MAX = 128          # CMHSE_TOPK_MAX
 
 
 class StepLosses(ctypes.Structure):
@@ -94,6 +95,10 @@ SIGNATURES = {
     'cmhse_sim_rank_ex': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                          c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                          c_void_p]),
+    'cmhse_sim_topk_workspace': (c_size_t, [c_int32, c_int32, c_int32]),
+    'cmhse_sim_topk': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                      c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     'cmhse_cosine_sim': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                         c_void_p]),
     'cmhse_contrastive_workspace': (c_size_t, [c_int32]),

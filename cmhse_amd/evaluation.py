@@ -831,6 +831,25 @@ def _from_last_encode(images, captions):
   return None
 
 
+def retrieve(queries, gallery, k=10):
+  """Top-k retrieval: for every query row, the k gallery rows with the largest dot product
+  (cosine similarity on encode_data's normalised embeddings), best first, smaller gallery index
+  first on exact ties (ops.sim_topk: matrix-free, exact fp32).
+
+    vid, para, *_ = encode_data(opt, model, loader)
+    scores, index = retrieve(para, vid, k)   # the k best videos for each paragraph
+    scores, index = retrieve(vid, para, k)   # the k best paragraphs for each video
+
+  NumPy in (encode_data's arrays, pinned views included), NumPy out: scores float32 [n, k] and
+  index int64 [n, k].  GPU tensors in: device tensors out (float32, int32), on the current
+  stream.  The ranking cache i2t / t2i serve from is neither read nor changed."""
+  if isinstance(queries, torch.Tensor) and queries.is_cuda:
+    return ops.sim_topk(queries, _as_device(gallery, queries.device), k)
+  q = _as_device(queries)
+  scores, index = ops.sim_topk(q, _as_device(gallery, q.device), k)
+  return scores.cpu().numpy(), index.cpu().numpy().astype(numpy.int64)
+
+
 def _rank_report(queries, gallery):
   rank, top1 = ops.sim_rank(_as_device(queries), _as_device(gallery))
   ranks = rank.cpu().numpy().astype(numpy.float64)      # the reference stores ranks in float64

@@ -784,6 +784,35 @@ def sim_rank(a, b, row0=0, nrows=None):
   return rank, top1
 
 
+def sim_topk(queries, gallery, k, row0=0, nrows=None):
+  """The k best gallery rows of each query row of the stripe [row0, row0+nrows) under the dot
+  product (cmhse_sim_topk): (scores float32 [nrows, k], index int32 [nrows, k]) device tensors,
+  score descending, smaller index first on exact ties; the scores are bit-identical to the
+  matching entries of cosine_sim(queries, gallery).  Exact fp32 whatever math_mode() says."""
+  lib = _lib.load()
+  a = _f32c(queries, 'queries')
+  b = _f32c(gallery, 'gallery')
+  N, D = a.shape
+  M = b.shape[0]
+  if b.shape[1] != D:
+    raise ValueError('embedding widths differ')
+  if nrows is None:
+    nrows = N - row0
+  k = int(k)
+  if not 1 <= k <= min(M, _lib.TOPK_MAX):
+    raise ValueError('k must lie in [1, min(gallery rows, %d)], got %d' % (_lib.TOPK_MAX, k))
+  scores = torch.empty(nrows, k, dtype=torch.float32, device=a.device)
+  index = torch.empty(nrows, k, dtype=torch.int32, device=a.device)
+  if nrows == 0:
+    return scores, index
+  ws_bytes = lib.cmhse_sim_topk_workspace(nrows, M, k)
+  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+  rc = lib.cmhse_sim_topk(a.data_ptr(), b.data_ptr(), N, M, D, row0, nrows, k, scores.data_ptr(),
+                          index.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+  _lib.check(rc, 'cmhse_sim_topk')
+  return scores, index
+
+
 def cosine_sim(im, s):
   """loss.cosine_sim on device: im @ s.T, exact fp32 (cmhse_cosine_sim)."""
   lib = _lib.load()

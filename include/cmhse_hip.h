@@ -286,6 +286,25 @@ int cmhse_sim_rank_ex(const float* A, const float* B, int32_t N, int32_t M, int3
                       int32_t row0, int32_t nrows, int32_t* rank, int32_t* top1, void* workspace,
                       size_t workspace_bytes, void* stream, void* timer);
 
+/* Top-K retrieval (no reference counterpart: what a user of a trained model asks first — the K
+ * best videos for a paragraph, or the reverse).  For each row i of the stripe [row0, row0+nrows)
+ * of d = A B^T (A [N,D] queries, B [M,D] gallery, exact-fp32 MFMA whatever the math mode):
+ *   index[i - row0, :]  the K columns j with the largest d[i,j], by score descending, then by j
+ *                       ascending on exact ties (the top1 rule of cmhse_sim_rank: the order of the
+ *                       64-bit key (ordered bits of d[i,j]) << 32 | (0xFFFFFFFF - j), unique per row,
+ *                       so the result depends on neither tiling nor scheduling);
+ *   scores[i - row0, :] their scores, bit-identical to the same entries of cmhse_cosine_sim(A, B).
+ * 1 <= K <= min(M, CMHSE_TOPK_MAX); K == M is a full stable descending sort of the row.  The N x M
+ * matrix is never materialised; the workspace holds K keys per row for each of a few column panels,
+ * a count fixed by nrows and K (LDS occupancy), not by M — 12 MB at nrows 4917, M 4917 or 10^6, K 50.
+ * nrows == 0: nothing is launched (scores, index, workspace may be NULL).  Inputs are assumed finite;
+ * otherwise the order is unspecified, but every index written lies in [0, M). */
+#define CMHSE_TOPK_MAX 128
+size_t cmhse_sim_topk_workspace(int32_t nrows, int32_t M, int32_t K);
+int cmhse_sim_topk(const float* A, const float* B, int32_t N, int32_t M, int32_t D, int32_t row0,
+                   int32_t nrows, int32_t K, float* scores /*[nrows,K]*/, int32_t* index /*[nrows,K]*/,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* Replaces loss.cosine_sim (loss.py:12-13): scores[n,m] = im s^T, exact fp32. */
 int cmhse_cosine_sim(const float* im, const float* s, int32_t n, int32_t m, int32_t D,
                      float* scores, void* stream);
