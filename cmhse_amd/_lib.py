@@ -58,6 +58,12 @@ class GruBwdJob(ctypes.Structure):
 
 STEP_LOSS_MAX = 8       # CMHSE_STEP_LOSS_MAX
 TOPK_MAX = 128          # CMHSE_TOPK_MAX
+GROUP_MEAN, GROUP_MAX = 0, 1     # CMHSE_GROUP_MEAN / CMHSE_GROUP_MAX
+GROUP_TILE_ROWS = 128   # the longest video / paragraph cmhse_group_plan packs
+
+
+def group_plan_max(B):
+  return 4 * B + 9      # CMHSE_GROUP_PLAN_MAX(B)
 
 
 class StepLosses(ctypes.Structure):
@@ -99,6 +105,13 @@ SIGNATURES = {
     'cmhse_sim_topk': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                       c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    'cmhse_group_plan': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32]),
+    'cmhse_group_scores': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                          c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    'cmhse_group_rank_workspace': (c_size_t, [c_int32]),
+    'cmhse_group_rank': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                        c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'cmhse_cosine_sim': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                         c_void_p]),
     'cmhse_contrastive_workspace': (c_size_t, [c_int32]),

@@ -850,6 +850,35 @@ def retrieve(queries, gallery, k=10):
   return scores.cpu().numpy(), index.cpu().numpy().astype(numpy.int64)
 
 
+def group_i2t_t2i(clip_embs, cap_embs, num_clips, num_caps=None, reduce='max'):
+  """Video <-> paragraph ranking by the group-wise score of the low level (the score
+  GroupWiseContrastiveLoss trains on: block max of the clip x caption scores of a (video, paragraph)
+  pair with max_violation, block mean without), from encode_data's clip and caption rows and
+  num_clips_total:
+
+    vid, para, clip, cap, _, _, nclips, _ = encode_data(opt, model, loader)
+    (r_v2p, top1_v2p, ranks_v2p), (r_p2v, top1_p2v, ranks_p2v) = group_i2t_t2i(
+        clip, cap, nclips, reduce='max' if opt.max_violation else 'mean')
+
+  Returns ((report, top1, ranks) video -> paragraph, the same paragraph -> video), each in the format
+  of i2t / t2i (report_from_ranks; top1 and ranks float64 NumPy), with one device-to-host copy.
+  num_caps defaults to num_clips.  GPU tensors in: top1 and ranks stay int32 device tensors (the
+  reports still come from one host copy).  The ranking cache i2t / t2i serve from is neither read nor
+  changed."""
+  on_device = isinstance(clip_embs, torch.Tensor) and clip_embs.is_cuda
+  if reduce not in ('max', 'mean'):
+    raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
+  ops.group_plan(num_clips, num_caps, len(clip_embs), len(cap_embs))   # argument errors before the upload
+  c = _as_device(clip_embs)
+  s = _as_device(cap_embs, c.device)
+  r_v, t_v, r_p, t_p = ops.group_rank(c, s, num_clips, num_caps, reduce)
+  host = torch.stack([r_v, t_v, r_p, t_p]).cpu().numpy().astype(numpy.float64)
+  if on_device:
+    return ((report_from_ranks(host[0]), t_v, r_v), (report_from_ranks(host[2]), t_p, r_p))
+  return ((report_from_ranks(host[0]), host[1], host[0]),
+          (report_from_ranks(host[2]), host[3], host[2]))
+
+
 def _rank_report(queries, gallery):
   rank, top1 = ops.sim_rank(_as_device(queries), _as_device(gallery))
   ranks = rank.cpu().numpy().astype(numpy.float64)      # the reference stores ranks in float64

@@ -813,6 +813,100 @@ def sim_topk(queries, gallery, k, row0=0, nrows=None):
   return scores, index
 
 
+_GROUP_REDUCE = {'max': _lib.GROUP_MAX, 'mean': _lib.GROUP_MEAN}
+
+
+def _group_counts(counts, name):
+  if isinstance(counts, torch.Tensor):
+    counts = counts.detach().cpu().numpy()
+  c = np.asarray(counts)
+  if c.ndim != 1 or c.size == 0:
+    raise ValueError('%s must be a non-empty 1-D sequence of counts' % name)
+  if not (np.issubdtype(c.dtype, np.integer) or (np.issubdtype(c.dtype, np.floating) and
+                                                 np.array_equal(c, np.floor(c)))):
+    raise ValueError('%s must hold whole numbers' % name)
+  c = c.astype(np.int64)
+  if (c < 1).any():
+    raise ValueError('%s: every video / paragraph needs at least one row' % name)
+  return c
+
+
+def group_plan(num_clips, num_caps, n_clip_rows, n_cap_rows):
+  """The host tile plan of cmhse_group_plan (int32 NumPy) for these counts; ValueError when the
+  counts do not tile the rows or a video / paragraph is longer than a tile (128 rows).  No GPU."""
+  nclips = _group_counts(num_clips, 'num_clips')
+  ncaps = nclips if num_caps is None else _group_counts(num_caps, 'num_caps')
+  B = nclips.size
+  if ncaps.size != B:
+    raise ValueError('num_caps has %d entries, num_clips %d' % (ncaps.size, B))
+  if int(nclips.sum()) != n_clip_rows or int(ncaps.sum()) != n_cap_rows:
+    raise ValueError('the counts must tile the rows: sum(num_clips) = %d for %d clip rows, '
+                     'sum(num_caps) = %d for %d caption rows'
+                     % (nclips.sum(), n_clip_rows, ncaps.sum(), n_cap_rows))
+  longest = max(int(nclips.max()), int(ncaps.max()))
+  if longest > _lib.GROUP_TILE_ROWS:
+    raise ValueError('a video or paragraph of %d rows: group scores support at most %d'
+                     % (longest, _lib.GROUP_TILE_ROWS))
+  off = np.zeros((2, B + 1), dtype=np.int32)
+  np.cumsum(nclips, out=off[0, 1:])
+  np.cumsum(ncaps, out=off[1, 1:])
+  plan = np.empty(_lib.group_plan_max(B), dtype=np.int32)
+  n = _lib.load().cmhse_group_plan(off[0].ctypes.data, off[1].ctypes.data, B, plan.ctypes.data,
+                                   plan.size)
+  _lib.check(min(n, 0), 'cmhse_group_plan')
+  return plan[:n]
+
+
+def _group_args(clips, caps, num_clips, num_caps, reduce):
+  if reduce not in _GROUP_REDUCE:
+    raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
+  for t, name in ((clips, 'clips'), (caps, 'caps')):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+      raise ValueError('%s must be a 2-D tensor' % name)
+  if clips.shape[1] != caps.shape[1]:
+    raise ValueError('embedding widths differ')
+  plan = group_plan(num_clips, num_caps, clips.shape[0], caps.shape[0])
+  c = _f32c(clips, 'clips')
+  s = _f32c(caps, 'caps')
+  return c, s, plan, upload(plan, c.device)
+
+
+def group_scores(clips, caps, num_clips, num_caps=None, reduce='max'):
+  """G [B, B] float32 on the device (cmhse_group_scores): G[i, j] reduces the scores clips[r] .
+  caps[c] over the clips of video i and the captions of paragraph j — the block max ('max') or the
+  block mean ('mean': fp64 sum in row-major order, / count, rounded to fp32), the score
+  GroupWiseContrastiveLoss trains on.  num_caps defaults to num_clips.  Exact fp32 whatever
+  math_mode() says; the clip x caption matrix is never stored."""
+  lib = _lib.load()
+  c, s, plan, plan_d = _group_args(clips, caps, num_clips, num_caps, reduce)
+  B = int(plan[0])
+  G = torch.empty(B, B, dtype=torch.float32, device=c.device)
+  rc = lib.cmhse_group_scores(c.data_ptr(), s.data_ptr(), c.shape[0], s.shape[0], c.shape[1], B,
+                              plan.ctypes.data, plan_d.data_ptr(), plan.size, _GROUP_REDUCE[reduce],
+                              G.data_ptr(), _stream())
+  _lib.check(rc, 'cmhse_group_scores')
+  return G
+
+
+def group_rank(clips, caps, num_clips, num_caps=None, reduce='max'):
+  """sim_rank's ranks applied to group_scores' G with its diagonal (cmhse_group_rank):
+  (rank_v2p, top1_v2p, rank_p2v, top1_p2v) int32 [B] device tensors — rank_v2p[i] counts the
+  paragraphs j with G[i, j] > G[i, i], top1_v2p[i] is the j of the largest G[i, j] (smallest j on
+  ties); the p2v pair is the same over the columns."""
+  lib = _lib.load()
+  c, s, plan, plan_d = _group_args(clips, caps, num_clips, num_caps, reduce)
+  B = int(plan[0])
+  out = torch.empty(4, B, dtype=torch.int32, device=c.device)
+  ws_bytes = lib.cmhse_group_rank_workspace(B)
+  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=c.device)
+  rc = lib.cmhse_group_rank(c.data_ptr(), s.data_ptr(), c.shape[0], s.shape[0], c.shape[1], B,
+                            plan.ctypes.data, plan_d.data_ptr(), plan.size, _GROUP_REDUCE[reduce],
+                            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                            out[3].data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+  _lib.check(rc, 'cmhse_group_rank')
+  return out[0], out[1], out[2], out[3]
+
+
 def cosine_sim(im, s):
   """loss.cosine_sim on device: im @ s.T, exact fp32 (cmhse_cosine_sim)."""
   lib = _lib.load()

@@ -305,6 +305,52 @@ int cmhse_sim_topk(const float* A, const float* B, int32_t N, int32_t M, int32_t
                    int32_t nrows, int32_t K, float* scores /*[nrows,K]*/, int32_t* index /*[nrows,K]*/,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* Group-wise video <-> paragraph scores and ranking from the low-level rows (the score
+ * GroupWiseContrastiveLoss trains on, loss.py:26-41; upstream's validate() has its evaluation
+ * commented out, train.py:228-244).  clips [Nc, D] and caps [Ns, D] are encode_data's clip and
+ * caption rows (already normalised: nothing is normalised here); video b owns the clip rows
+ * [clip_off[b], clip_off[b+1]), paragraph b the caption rows [cap_off[b], cap_off[b+1]).
+ *   G[i, j]  over the block (clips of video i) x (captions of paragraph j) of the fp32 scores
+ *            clips[r] . caps[c] (exact-fp32 MFMA, each bit-identical to cmhse_cosine_sim's):
+ *            CMHSE_GROUP_MAX   the block maximum;
+ *            CMHSE_GROUP_MEAN  the scores summed in fp64 sequentially in row-major order (clip-major,
+ *                              then caption), divided in fp64 by the count, rounded to fp32 — for
+ *                              blocks of at most 256 entries the order of cmhse_groupwise_fwd's
+ *                              `reduced`, so bit-identical to it there.
+ * The clip x caption matrix never reaches HBM: whole videos are packed into row tiles of at most 128
+ * clip rows and whole paragraphs into column tiles of at most 128 caption rows, and each workgroup
+ * reduces the blocks of its tile in its epilogue (no atomics, no partials).
+ *
+ * cmhse_group_plan (host only, no GPU needed): from the host prefix sums clip_off_host[B+1] and
+ * cap_off_host[B+1] (0 first, strictly increasing: every count >= 1) fills plan[0, len) and returns
+ * len, or CMHSE_ERR_ARG (null pointer, B <= 0, bad prefix sums), CMHSE_ERR_UNSUPPORTED (a video or
+ * paragraph of more than 128 rows), CMHSE_ERR_WORKSPACE (plan_cap < CMHSE_GROUP_PLAN_MAX(B)).
+ * Layout (int32): B, Nc, Ns, R row tiles, C column tiles, clip_off[B+1], cap_off[B+1], the first
+ * video of each row tile [R+1] (ending in B), the first paragraph of each column tile [C+1].
+ * The caller uploads plan[0, len) to the device; the calls below take both copies: the host copy is
+ * validated in full (O(B)) and sizes the launch, the kernels read the device copy, which must hold
+ * the same values.  The count vectors need not be equal (num_caps != num_clips).
+ *
+ * cmhse_group_scores: G [B, B] row-major (video i, paragraph j).  No workspace.
+ * cmhse_group_rank: the ranks of cmhse_sim_rank applied to G with its diagonal —
+ *   rank_v2p[i] = #{j != i : G[i,j] > G[i,i]},  top1_v2p[i] = the j of the largest G[i,j], smallest j
+ *   on ties; rank_p2v / top1_p2v the same over the columns (j -> i).  G lives in the workspace
+ *   (cmhse_group_rank_workspace(B): B^2 floats + per-64-tile partials, 106 MB at B = 4917).
+ * Exact fp32 whatever the math mode.  Argument errors are returned before anything is launched. */
+#define CMHSE_GROUP_MEAN 0
+#define CMHSE_GROUP_MAX 1
+#define CMHSE_GROUP_PLAN_MAX(B) (4 * (B) + 9)
+int32_t cmhse_group_plan(const int32_t* clip_off_host, const int32_t* cap_off_host, int32_t B,
+                         int32_t* plan, int32_t plan_cap);
+int cmhse_group_scores(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                       int32_t B, const int32_t* plan_host, const int32_t* plan, int32_t plan_len,
+                       int32_t reduce, float* G /*[B,B]*/, void* stream);
+size_t cmhse_group_rank_workspace(int32_t B);
+int cmhse_group_rank(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                     int32_t B, const int32_t* plan_host, const int32_t* plan, int32_t plan_len,
+                     int32_t reduce, int32_t* rank_v2p, int32_t* top1_v2p, int32_t* rank_p2v,
+                     int32_t* top1_p2v, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Replaces loss.cosine_sim (loss.py:12-13): scores[n,m] = im s^T, exact fp32. */
 int cmhse_cosine_sim(const float* im, const float* s, int32_t n, int32_t m, int32_t D,
                      float* scores, void* stream);
