@@ -59,7 +59,7 @@ class GruBwdJob(ctypes.Structure):
 STEP_LOSS_MAX = 8       # CMHSE_STEP_LOSS_MAX
 TOPK_MAX = 128          # CMHSE_TOPK_MAX
 GROUP_MEAN, GROUP_MAX = 0, 1     # CMHSE_GROUP_MEAN / CMHSE_GROUP_MAX
-GROUP_TILE_ROWS = 128   # the longest video / paragraph cmhse_group_plan packs
+GROUP_TILE_ROWS = 128   # CMHSE_GROUP_TILE_ROWS: the longest video / paragraph cmhse_group_plan packs
 
 
 def group_plan_max(B):

@@ -10,15 +10,16 @@
 //   cmhse_group_plan    host only: packs WHOLE videos into row tiles of at most 128 clip rows and
 //                       whole paragraphs into column tiles of at most 128 caption rows, so every
 //                       block lies inside exactly one tile: no atomics, no partials, no combine.
-//   group_sim_kernel    one workgroup per (row tile, column tile): nt_phase unchanged (every score is
-//                       bit-identical to cmhse_cosine_sim's), then the tile's scores are staged in LDS
-//                       in two 64-row halves — in the tile buffers nt_phase has just freed — and each
-//                       (video, paragraph) block of the tile is reduced by one thread in the contract's
-//                       order; a block whose video straddles the halves carries its running fp64 sum
-//                       (and max) across in LDS, which keeps the order.
+//   group_sim_kernel    one workgroup per (row tile, column tile), dealt to the XCDs by score_tile.hpp:
+//                       nt_phase unchanged (every score is bit-identical to cmhse_cosine_sim's), then
+//                       the tile's scores are staged in LDS in two 64-row halves — in the tile buffers
+//                       nt_phase has just freed — and each (video, paragraph) block of the tile is
+//                       reduced by one thread in the contract's order; a block whose video straddles
+//                       the halves carries its running fp64 sum (and max) across in LDS, which keeps
+//                       the order.
 //   group_rank_kernel   64 x 64 tiles of the stored G: per row (video -> paragraph) and per column
 //                       (paragraph -> video) the count of entries above the diagonal and the top-1 key
-//                       (sim.hip's: ordered score bits, then the smaller index), one partial per tile;
+//                       (score_tile.hpp's score key), one partial per tile;
 //   group_rank_final_kernel   sums / maxes the partials of each row and column.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -26,37 +27,26 @@
 
 #include "../../include/cmhse_hip.h"
 #include "nt_core.hpp"
+#include "score_tile.hpp"
 
 namespace cmhse {
 namespace {
 
-typedef unsigned long long gkey_t;
-
-constexpr int kGrBM = 128;                 // clip rows per row tile (at most)
-constexpr int kGrBN = 128;                 // caption rows per column tile (at most)
+constexpr int kGrBM = CMHSE_GROUP_TILE_ROWS;   // clip rows per row tile (at most)
+constexpr int kGrBN = CMHSE_GROUP_TILE_ROWS;   // caption rows per column tile (at most)
 constexpr int kGrHdr = 5;                  // plan header: B, Nc, Ns, row tiles, column tiles
 constexpr int kGrLd = kGrBN + 4;           // staged score row stride (floats)
-// Staged rows per pass.  64: two halves in the freed tile buffers (40 KB of LDS in all, the occupancy
-// of sim_rank's counting pass).  128 (A/B builds only, -DCMHSE_GROUP_FULL_STAGE): one pass over a
-// separate 66 KB stage beside the tile buffers — DESIGN.md §4 has the numbers of both.
-#ifdef CMHSE_GROUP_FULL_STAGE
-constexpr int kGrStageRows = 128;
-constexpr size_t kGrStageOff = TileSmem<kGrBM, kGrBN>::kBytes;
-#else
+// Staged rows per pass: two 64-row halves in the freed tile buffers (40 KB of LDS in all, the
+// occupancy of sim_rank's counting pass; one 128-row stage beside them measured slower: DESIGN.md §4).
 constexpr int kGrStageRows = 64;
-constexpr size_t kGrStageOff = 0;
-#endif
 constexpr size_t kGrStageBytes = sizeof(float) * kGrStageRows * kGrLd;
-constexpr size_t kGrCarryOff = kGrStageOff + kGrStageBytes;                   // double [kGrBN]
+constexpr size_t kGrCarryOff = kGrStageBytes;                                 // double [kGrBN]
 constexpr size_t kGrCmaxOff = kGrCarryOff + sizeof(double) * kGrBN;           // float [kGrBN]
 constexpr size_t kGrVoffOff = kGrCmaxOff + sizeof(float) * kGrBN;             // int [kGrBM + 1]
 constexpr size_t kGrPoffOff = kGrVoffOff + sizeof(int32_t) * (kGrBM + 1);     // int [kGrBN + 1]
 constexpr size_t kGrEpiBytes = kGrPoffOff + sizeof(int32_t) * (kGrBN + 1);
-constexpr size_t kGrSmem =
-    kGrEpiBytes > TileSmem<kGrBM, kGrBN>::kBytes ? kGrEpiBytes : TileSmem<kGrBM, kGrBN>::kBytes;
-#ifndef CMHSE_GROUP_FULL_STAGE
-static_assert(kGrSmem == TileSmem<kGrBM, kGrBN>::kBytes, "the epilogue must fit in the freed tile buffers");
-#endif
+constexpr size_t kGrSmem = TileSmem<kGrBM, kGrBN>::kBytes;
+static_assert(kGrEpiBytes <= kGrSmem, "the epilogue must fit in the freed tile buffers");
 
 constexpr int kGrRankT = 64;               // G tile of the rank kernel
 
@@ -73,25 +63,16 @@ struct GroupParams {
   float* G;                // [B, B]
 };
 
-__device__ __forceinline__ unsigned g_ordered_bits(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void group_sim_kernel(const GroupParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, srow = tid >> 2;
   int rt, ct;
   if (p.group > 0) {
-    // XCD-aware deal of sim.hip's counting pass: groups of G row tiles x one column tile, group Q
-    // to XCD label Q % 8 (blocks b, b + 8 share an XCD), its G workgroups back to back there, so a
-    // caption tile crosses the fabric once per group and the group's clip tiles stay L2-resident
-    const int G = p.group;
-    const int x = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int Q = (q / G) * 8 + x;
-    rt = G * (Q / p.col_tiles) + (q % G);
-    ct = Q % p.col_tiles;
+    // a caption tile crosses the fabric once per group, the group's clip tiles stay L2-resident
+    const TileIdx t = xcd_deal_tile(blockIdx.x, p.group, p.col_tiles);
+    rt = t.rt;
+    ct = t.ct;
     if (rt >= p.row_tiles) return;   // padding of the last row group / the grid
   } else {
     rt = blockIdx.x / p.col_tiles;
@@ -110,24 +91,16 @@ __global__ __launch_bounds__(kThreads) void group_sim_kernel(const GroupParams p
   rowaddr_t ar[kGrBM / 64], br[kGrBN / 64];
   bool av[kGrBM / 64], bv[kGrBN / 64];
 #pragma unroll
-  for (int i = 0; i < kGrBM / 64; ++i) {
-    const int li = srow + 64 * i;
-    av[i] = li < nr;
-    ar[i] = row_addr(p.C + static_cast<int64_t>(r_begin + (av[i] ? li : 0)) * p.D);
-  }
+  for (int i = 0; i < kGrBM / 64; ++i) ar[i] = tile_row(p.C, p.D, r_begin, srow + 64 * i, nr, &av[i]);
 #pragma unroll
-  for (int i = 0; i < kGrBN / 64; ++i) {
-    const int lj = srow + 64 * i;
-    bv[i] = lj < nc;
-    br[i] = row_addr(p.S + static_cast<int64_t>(c_begin + (bv[i] ? lj : 0)) * p.D);
-  }
+  for (int i = 0; i < kGrBN / 64; ++i) br[i] = tile_row(p.S, p.D, c_begin, srow + 64 * i, nc, &bv[i]);
   f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
   const int b_row0[2] = {wn * 64, wn * 64 + 32};
   // ends with a barrier: every wave is done with the tile buffers
   nt_phase<kGrBM, kGrBN, 2, 2, 2, 1, VEC>(smem, ar, av, br, bv, p.D, wm * 64, b_row0, acc);
 
   char* lds = reinterpret_cast<char*>(smem);
-  float* stage = reinterpret_cast<float*>(lds + kGrStageOff);
+  float* stage = smem;
   double* carry = reinterpret_cast<double*>(lds + kGrCarryOff);
   float* cmax = reinterpret_cast<float*>(lds + kGrCmaxOff);
   int* s_voff = reinterpret_cast<int*>(lds + kGrVoffOff);
@@ -201,17 +174,17 @@ struct GroupRankParams {
   const float* G;          // [B, B]
   int32_t B, tiles;        // tiles = ceil(B / 64)
   int32_t* cnt_row;        // [tiles (column tile), B]
-  gkey_t* key_row;
+  score_key_t* key_row;
   int32_t* cnt_col;        // [tiles (row tile), B]
-  gkey_t* key_col;
+  score_key_t* key_col;
   int32_t *rank_v2p, *top1_v2p, *rank_p2v, *top1_p2v;
 };
 
 // count of x > d (x at an index other than `self`) and the top-1 key over the 64 lanes of a wave
 __device__ __forceinline__ void wave_rank64(float x, bool valid, bool self, float d, int idx0, int* cnt,
-                                            gkey_t* key) {
+                                            score_key_t* key) {
   const unsigned long long gt = __ballot(valid && !self && x > d);
-  const unsigned ob = valid ? g_ordered_bits(x) : 0u;
+  const unsigned ob = valid ? ordered_bits(x) : 0u;
   unsigned obmax = ob;
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) {
@@ -221,7 +194,7 @@ __device__ __forceinline__ void wave_rank64(float x, bool valid, bool self, floa
   const unsigned long long eq = __ballot(valid && ob == obmax);
   const int best = idx0 + (__ffsll(static_cast<long long>(eq)) - 1);
   *cnt = __popcll(gt);
-  *key = (static_cast<gkey_t>(obmax) << 32) | static_cast<gkey_t>(0xFFFFFFFFu - static_cast<unsigned>(best));
+  *key = bits_key(obmax, best);
 }
 
 __global__ __launch_bounds__(kThreads) void group_rank_kernel(const GroupRankParams p) {
@@ -247,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void group_rank_kernel(const GroupRankPar
   for (int k = 0; k < kPerWave; ++k) {
     const int rr = wave * kPerWave + k;
     int cnt;
-    gkey_t key;
+    score_key_t key;
     // row i = i0 + rr against the tile's 64 columns (lane = column)
     if (i0 + rr < p.B) {   // (wave-uniform)
       const int j = j0 + lane;
@@ -276,20 +249,18 @@ __global__ void group_rank_final_kernel(const GroupRankParams p) {
   const bool col = t >= p.B;
   const int i = col ? t - p.B : t;
   const int32_t* cnt = col ? p.cnt_col : p.cnt_row;
-  const gkey_t* key = col ? p.key_col : p.key_row;
+  const score_key_t* key = col ? p.key_col : p.key_row;
   int c = 0;
-  gkey_t k = 0;
+  score_key_t k = 0;
   for (int q = 0; q < p.tiles; ++q) {
     const int64_t e = static_cast<int64_t>(q) * p.B + i;
     c += cnt[e];
     k = key[e] > k ? key[e] : k;
   }
-  const int32_t top1 = static_cast<int32_t>(0xFFFFFFFFu - static_cast<unsigned>(k & 0xFFFFFFFFull));
+  const int32_t top1 = key_index(k);
   (col ? p.rank_p2v : p.rank_v2p)[i] = c;
   (col ? p.top1_p2v : p.top1_v2p)[i] = top1;
 }
-
-size_t g_align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // prefix sums of B >= 1 positive counts, Nc / Ns at the end
 bool offsets_ok(const int32_t* off, int32_t B) {
@@ -359,31 +330,11 @@ int launch_group_sim(const float* clips, const float* caps, int32_t D, int32_t B
   p.rt_vid = p.cap_off + B + 1;
   p.ct_par = p.rt_vid + p.row_tiles + 1;
   p.G = G;
-  // sim_rank's deal (sim.hip, cmhse_sim_rank_ex): the largest G of 4, 3, 2 that keeps every XCD within
-  // the rounds of resident workgroups a perfectly even deal needs (96 per XCD: 3 per CU)
-  const int64_t tiles = static_cast<int64_t>(p.row_tiles) * p.col_tiles;
-  const int64_t ideal_rounds = (tiles + 767) / 768;
-  int grp = 0;
-  for (int g = 4; g >= 2 && grp == 0; --g) {
-    const int64_t groups = static_cast<int64_t>((p.row_tiles + g - 1) / g) * p.col_tiles;
-    if (((groups + 7) / 8 * g + 95) / 96 <= ideal_rounds) grp = g;
-  }
-  p.group = grp;
-  int64_t blocks = tiles;
-  if (grp > 0) blocks = (static_cast<int64_t>((p.row_tiles + grp - 1) / grp) * p.col_tiles + 7) / 8 * 8 * grp;
-  if (blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
-  const void* fn = (D % 4 == 0) ? reinterpret_cast<const void*>(&group_sim_kernel<true>)
-                                : reinterpret_cast<const void*>(&group_sim_kernel<false>);
-  if (kGrSmem > 64 * 1024 &&
-      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kGrSmem)) != hipSuccess)
-    return CMHSE_ERR_LAUNCH;
-  if (D % 4 == 0)
-    hipLaunchKernelGGL(group_sim_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), kGrSmem,
-                       stream, p);
-  else
-    hipLaunchKernelGGL(group_sim_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), kGrSmem,
-                       stream, p);
-  return CMHSE_OK;
+  const XcdDeal deal = xcd_deal(p.row_tiles, p.col_tiles);
+  p.group = deal.group;
+  if (deal.blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  return launch_tiles(group_sim_kernel<true>, group_sim_kernel<false>, D, dim3(static_cast<unsigned>(deal.blocks)),
+                      kGrSmem, stream, p);
 }
 
 }  // namespace
@@ -429,8 +380,8 @@ extern "C" size_t cmhse_group_rank_workspace(int32_t B) {
   if (B <= 0) return 0;
   const size_t tiles = (static_cast<size_t>(B) + kGrRankT - 1) / kGrRankT;
   const size_t part = tiles * static_cast<size_t>(B);
-  return g_align256(static_cast<size_t>(B) * static_cast<size_t>(B) * sizeof(float)) +
-         2 * (g_align256(part * sizeof(int32_t)) + g_align256(part * sizeof(gkey_t)));
+  return align256(static_cast<size_t>(B) * static_cast<size_t>(B) * sizeof(float)) +
+         2 * (align256(part * sizeof(int32_t)) + align256(part * sizeof(score_key_t)));
 }
 
 extern "C" int cmhse_group_rank(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
@@ -448,15 +399,15 @@ extern "C" int cmhse_group_rank(const float* clips, const float* caps, int32_t N
   char* ws = static_cast<char*>(workspace);
   GroupRankParams rp;
   rp.G = reinterpret_cast<float*>(ws);
-  ws += g_align256(static_cast<size_t>(B) * static_cast<size_t>(B) * sizeof(float));
+  ws += align256(static_cast<size_t>(B) * static_cast<size_t>(B) * sizeof(float));
   const size_t part = static_cast<size_t>(tiles) * static_cast<size_t>(B);
   rp.cnt_row = reinterpret_cast<int32_t*>(ws);
-  ws += g_align256(part * sizeof(int32_t));
-  rp.key_row = reinterpret_cast<gkey_t*>(ws);
-  ws += g_align256(part * sizeof(gkey_t));
+  ws += align256(part * sizeof(int32_t));
+  rp.key_row = reinterpret_cast<score_key_t*>(ws);
+  ws += align256(part * sizeof(score_key_t));
   rp.cnt_col = reinterpret_cast<int32_t*>(ws);
-  ws += g_align256(part * sizeof(int32_t));
-  rp.key_col = reinterpret_cast<gkey_t*>(ws);
+  ws += align256(part * sizeof(int32_t));
+  rp.key_col = reinterpret_cast<score_key_t*>(ws);
   rp.B = B;
   rp.tiles = tiles;
   rp.rank_v2p = rank_v2p;

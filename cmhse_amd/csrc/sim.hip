@@ -3,7 +3,9 @@
 //   cmhse_sim_rank        evaluation.i2t / t2i  (/root/reference/evaluation.py:160-213):
 //                         numpy.dot + per-row numpy.argsort become one exact-fp32 MFMA GEMM whose
 //                         epilogue counts, per row, the columns that beat the diagonal and tracks
-//                         the arg-max column — the N x M matrix never reaches HBM.
+//                         the arg-max column — the N x M matrix never reaches HBM.  Its top-1 key,
+//                         operand rows and XCD-grouped deal of the tiles are score_tile.hpp's, shared
+//                         with topk.hip and group.hip.
 //   cmhse_cosine_sim      loss.cosine_sim       (/root/reference/loss.py:12-13)
 //   cmhse_contrastive_fwd loss.ContrastiveLoss.forward (/root/reference/loss.py:86-117)
 //
@@ -19,6 +21,7 @@
 #include "../../include/cmhse_hip.h"
 #include "gru_ws.hpp"
 #include "nt_core.hpp"
+#include "score_tile.hpp"
 #include "step_loss.hpp"
 
 namespace cmhse {
@@ -33,26 +36,16 @@ struct SimParams {
   const float* A;  // [N, D]
   const float* B;  // [M, D]
   int32_t N, M, D, row0, nrows, n_tiles;
-  int32_t m_tiles8;             // counting pass: row tiles per rasterisation group (see sim_kernel), 0 = plain
+  int32_t group;                // counting pass: row tiles per XCD group (xcd_deal), 0 = plain row-major order
   float* diag;                  // [nrows]
   int32_t* rank;                // [nrows]
-  unsigned long long* top1key;  // [nrows]
+  score_key_t* top1key;         // [nrows]
   float* scores;                // [nrows, M] (kSimStore)
   // batched square blocks (blockIdx.y = block): rows/cols [blk_off[b], blk_off[b+1]) of A and B,
   // scores of block b at scores + b * blk_stride, leading dimension = the block's size
   const int32_t* blk_off;
   int64_t blk_stride;
 };
-
-__device__ __forceinline__ bool aligned16s(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
-// monotone map float -> uint32 (total order of non-NaN floats)
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // TS = 32 x 32 blocks per wave in each direction: 2 = the 128 x 128 tile; 1 = a 64 x 64 tile for the
 // small matrices of the training losses (n = 32 ... ~130: ONE 128 x 128 workgroup there is a
@@ -108,23 +101,11 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
   if (MODE == kSimDiag) {
     i0 = blockIdx.x * BM;
     j0 = p.row0 + i0;  // the column block that holds this row block's diagonal
-  } else if (MODE == kSimRank && p.m_tiles8 > 0) {
-    // Counting pass, XCD-aware: blocks b, b + 8 share an XCD (round-robin dispatch), whose 4 MB L2
-    // holds neither operand (2 x 20 MB at N = 4917).  The tiles are dealt in GROUPS — G consecutive
-    // row tiles x one column tile — group Q to XCD label Q % 8, its G workgroups back to back in
-    // that XCD's order: they run together and pull their B tile through the fabric once instead of
-    // G times, and the G A tiles of a row group stay L2-resident while the group's column tiles
-    // stream by (931 -> 424 MB per launch at N = 4917, rocprofv3 FETCH_SIZE).  G is the largest of
-    // 4, 3, 2 that keeps every XCD within the rounds of resident workgroups a perfectly even deal
-    // needs: a launch is two rounds at N = 4917, and one XCD with a handful of workgroups in a
-    // third round costs a third of the launch (0.70 ms with a deal by row tile, 0.49 with G = 4,
-    // against 0.45 ms).
-    const int G = p.m_tiles8;      // row tiles per group (2..4), chosen by the launcher
-    const int x = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int Q = (q / G) * 8 + x;
-    const int it = G * (Q / p.n_tiles) + (q % G);
-    j0 = (Q % p.n_tiles) * BN;
-    i0 = it * BM;
+  } else if (MODE == kSimRank && p.group > 0) {
+    // counting pass: the XCD-grouped deal (score_tile.hpp)
+    const TileIdx t = xcd_deal_tile(blockIdx.x, p.group, p.n_tiles);
+    j0 = t.ct * BN;
+    i0 = t.rt * BM;
     if (i0 >= p.nrows) return;     // padding: groups beyond the last row group, rows of a partial group
   } else {
     j0 = (blockIdx.x % p.n_tiles) * BN;
@@ -134,17 +115,9 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
   rowaddr_t br[BN / 64];
   bool av[BM / 64], bv[BN / 64];
 #pragma unroll
-  for (int i = 0; i < BM / 64; ++i) {
-    const int li = i0 + srow + 64 * i;
-    av[i] = li < p.nrows;
-    ar[i] = row_addr(p.A + static_cast<int64_t>(p.row0 + (av[i] ? li : 0)) * p.D);
-  }
+  for (int i = 0; i < BM / 64; ++i) ar[i] = tile_row(p.A, p.D, p.row0, i0 + srow + 64 * i, p.nrows, &av[i]);
 #pragma unroll
-  for (int i = 0; i < BN / 64; ++i) {
-    const int j = j0 + srow + 64 * i;
-    bv[i] = j < p.M;
-    br[i] = row_addr(p.B + static_cast<int64_t>(bv[i] ? j : 0) * p.D);
-  }
+  for (int i = 0; i < BN / 64; ++i) br[i] = tile_row(p.B, p.D, 0, j0 + srow + 64 * i, p.M, &bv[i]);
   f32x16 acc[TS][TS];
 #pragma unroll
   for (int ms = 0; ms < TS; ++ms)
@@ -230,9 +203,7 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
         }
         if (rok && (lane & 31) == 0) {
           if (cnt) atomicAdd(&p.rank[li], cnt);
-          if (jbest >= 0)
-            atomicMax(&p.top1key[li], (static_cast<unsigned long long>(obmax) << 32) |
-                                          static_cast<unsigned long long>(0xFFFFFFFFu - static_cast<unsigned>(jbest)));
+          if (jbest >= 0) atomicMax(&p.top1key[li], bits_key(obmax, jbest));
         }
       }
     }
@@ -243,9 +214,9 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
 #endif
 }
 
-__global__ void top1_finalize_kernel(const unsigned long long* key, int32_t* top1, int n) {
+__global__ void top1_finalize_kernel(const score_key_t* key, int32_t* top1, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) top1[i] = static_cast<int32_t>(0xFFFFFFFFu - static_cast<unsigned>(key[i] & 0xFFFFFFFFull));
+  if (i < n) top1[i] = key_index(key[i]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -353,8 +324,6 @@ __global__ void contrastive_final_kernel(const LossParams p_) {
   }
 }
 
-static inline size_t align_up_(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 static int launch_sim_store(const float* A, const float* B, int n, int m, int D, float* scores,
                             hipStream_t stream) {
   SimParams p;
@@ -368,7 +337,7 @@ static int launch_sim_store(const float* A, const float* B, int n, int m, int D,
   const bool small = n <= kSimSmallMax && m <= kSimSmallMax;   // training-loss sizes: 64 x 64 tiles
   const int bt = small ? 64 : kSimBN;
   p.n_tiles = (m + bt - 1) / bt;
-  p.m_tiles8 = 0;
+  p.group = 0;
   p.diag = nullptr;
   p.rank = nullptr;
   p.top1key = nullptr;
@@ -379,15 +348,9 @@ static int launch_sim_store(const float* A, const float* B, int n, int m, int D,
   if (blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
   const size_t smem = small ? TileSmem<64, 64>::kBytes : TileSmem<kSimBM, kSimBN>::kBytes;
   const dim3 grid(static_cast<unsigned>(blocks));
-  if (small && D % 4 == 0)
-    hipLaunchKernelGGL((sim_kernel<kSimStore, true, 1>), grid, dim3(kThreads), smem, stream, p);
-  else if (small)
-    hipLaunchKernelGGL((sim_kernel<kSimStore, false, 1>), grid, dim3(kThreads), smem, stream, p);
-  else if (D % 4 == 0)
-    hipLaunchKernelGGL((sim_kernel<kSimStore, true>), grid, dim3(kThreads), smem, stream, p);
-  else
-    hipLaunchKernelGGL((sim_kernel<kSimStore, false>), grid, dim3(kThreads), smem, stream, p);
-  return CMHSE_OK;
+  if (small)
+    return launch_tiles(sim_kernel<kSimStore, true, 1>, sim_kernel<kSimStore, false, 1>, D, grid, smem, stream, p);
+  return launch_tiles(sim_kernel<kSimStore, true>, sim_kernel<kSimStore, false>, D, grid, smem, stream, p);
 }
 
 }  // namespace cmhse
@@ -396,8 +359,8 @@ using namespace cmhse;
 
 extern "C" size_t cmhse_sim_rank_workspace(int32_t nrows) {
   if (nrows <= 0) return 0;
-  return align_up_(static_cast<size_t>(nrows) * sizeof(float), 256) +
-         align_up_(static_cast<size_t>(nrows) * sizeof(unsigned long long), 256);
+  return align256(static_cast<size_t>(nrows) * sizeof(float)) +
+         align256(static_cast<size_t>(nrows) * sizeof(score_key_t));
 }
 
 extern "C" int cmhse_sim_rank_ex(const float* A, const float* B, int32_t N, int32_t M, int32_t D,
@@ -422,42 +385,27 @@ extern "C" int cmhse_sim_rank_ex(const float* A, const float* B, int32_t N, int3
   p.nrows = nrows;
   p.n_tiles = (M + kSimBN - 1) / kSimBN;
   p.diag = static_cast<float*>(workspace);
-  p.top1key = reinterpret_cast<unsigned long long*>(
-      static_cast<char*>(workspace) + align_up_(static_cast<size_t>(nrows) * sizeof(float), 256));
+  p.top1key = reinterpret_cast<score_key_t*>(
+      static_cast<char*>(workspace) + align256(static_cast<size_t>(nrows) * sizeof(float)));
   p.rank = rank;
   p.scores = nullptr;
   p.blk_off = nullptr;
   p.blk_stride = 0;
   const int m_tiles = (nrows + kSimBM - 1) / kSimBM;
-  // groups of G row tiles x 1 column tile dealt round-robin to the 8 XCD labels (see sim_kernel);
-  // 96 = workgroups resident per XCD (3 per CU at 41 KB of LDS)
-  const int64_t tiles = static_cast<int64_t>(m_tiles) * p.n_tiles;
-  const int64_t ideal_rounds = (tiles + 767) / 768;
-  int G = 0;
-  for (int g = 4; g >= 2 && G == 0; --g) {
-    const int64_t groups = static_cast<int64_t>((m_tiles + g - 1) / g) * p.n_tiles;
-    if (((groups + 7) / 8 * g + 95) / 96 <= ideal_rounds) G = g;
-  }
-  p.m_tiles8 = G;
-  int64_t blocks = tiles;
-  if (G > 0) blocks = (static_cast<int64_t>((m_tiles + G - 1) / G) * p.n_tiles + 7) / 8 * 8 * G;
-  if (blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  const XcdDeal deal = xcd_deal(m_tiles, p.n_tiles);
+  p.group = deal.group;
+  if (deal.blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
   if (hipMemsetAsync(rank, 0, sizeof(int32_t) * nrows, stream) != hipSuccess) return CMHSE_ERR_LAUNCH;
-  if (hipMemsetAsync(p.top1key, 0, sizeof(unsigned long long) * nrows, stream) != hipSuccess)
+  if (hipMemsetAsync(p.top1key, 0, sizeof(score_key_t) * nrows, stream) != hipSuccess)
     return CMHSE_ERR_LAUNCH;
   const size_t smem = TileSmem<kSimBM, kSimBN>::kBytes;
   Timer* timer = static_cast<Timer*>(timer_);   // brackets the counting pass alone
-  if (D % 4 == 0) {
-    hipLaunchKernelGGL((sim_kernel<kSimDiag, true>), dim3(m_tiles), dim3(kThreads), smem, stream, p);
-    if (timer) (void)hipEventRecord(timer->start, stream);
-    hipLaunchKernelGGL((sim_kernel<kSimRank, true>), dim3(static_cast<unsigned>(blocks)),
-                       dim3(kThreads), smem, stream, p);
-  } else {
-    hipLaunchKernelGGL((sim_kernel<kSimDiag, false>), dim3(m_tiles), dim3(kThreads), smem, stream, p);
-    if (timer) (void)hipEventRecord(timer->start, stream);
-    hipLaunchKernelGGL((sim_kernel<kSimRank, false>), dim3(static_cast<unsigned>(blocks)),
-                       dim3(kThreads), smem, stream, p);
-  }
+  int rc = launch_tiles(sim_kernel<kSimDiag, true>, sim_kernel<kSimDiag, false>, D, dim3(m_tiles), smem, stream, p);
+  if (rc != CMHSE_OK) return rc;
+  if (timer) (void)hipEventRecord(timer->start, stream);
+  rc = launch_tiles(sim_kernel<kSimRank, true>, sim_kernel<kSimRank, false>, D,
+                    dim3(static_cast<unsigned>(deal.blocks)), smem, stream, p);
+  if (rc != CMHSE_OK) return rc;
   if (timer) {
     (void)hipEventRecord(timer->stop, stream);
     timer->launches = 1;
@@ -485,8 +433,8 @@ extern "C" int cmhse_cosine_sim(const float* im, const float* s, int32_t n, int3
 extern "C" size_t cmhse_contrastive_workspace(int32_t n) {
   if (n <= 0) return 0;
   const size_t nrb = (n + 63) / 64;
-  return align_up_(static_cast<size_t>(n) * n * sizeof(float), 256) +
-         align_up_(2 * nrb * sizeof(double), 256);
+  return align256(static_cast<size_t>(n) * n * sizeof(float)) +
+         align256(2 * nrb * sizeof(double));
 }
 
 extern "C" int cmhse_contrastive_fwd(const float* im, const float* s, int32_t n, int32_t D,
@@ -509,7 +457,7 @@ extern "C" int cmhse_contrastive_fwd(const float* im, const float* s, int32_t n,
   lp.max_violation = max_violation;
   lp.norm = norm;
   lp.partial = reinterpret_cast<double*>(static_cast<char*>(workspace) +
-                                         align_up_(static_cast<size_t>(n) * n * sizeof(float), 256));
+                                         align256(static_cast<size_t>(n) * n * sizeof(float)));
   lp.loss = loss;
   lp.blk_off = nullptr;
   lp.blk_stride = 0;
@@ -521,8 +469,8 @@ extern "C" int cmhse_contrastive_fwd(const float* im, const float* s, int32_t n,
 extern "C" size_t cmhse_contrastive_blocks_workspace(int32_t n_blocks, int32_t max_n) {
   if (n_blocks <= 0 || max_n <= 0) return 0;
   const size_t nrb = (max_n + 63) / 64;
-  return align_up_(static_cast<size_t>(n_blocks) * max_n * max_n * sizeof(float), 256) +
-         align_up_(static_cast<size_t>(n_blocks) * 2 * nrb * sizeof(double), 256);
+  return align256(static_cast<size_t>(n_blocks) * max_n * max_n * sizeof(float)) +
+         align256(static_cast<size_t>(n_blocks) * 2 * nrb * sizeof(double));
 }
 
 extern "C" int cmhse_contrastive_blocks_fwd(const float* im, const float* s,
@@ -547,7 +495,7 @@ extern "C" int cmhse_contrastive_blocks_fwd(const float* im, const float* s,
   const bool small = max_n <= kSimSmallMax;
   const int bt = small ? 64 : kSimBN;
   p.n_tiles = (max_n + bt - 1) / bt;
-  p.m_tiles8 = 0;
+  p.group = 0;
   p.diag = nullptr;
   p.rank = nullptr;
   p.top1key = nullptr;
@@ -556,18 +504,11 @@ extern "C" int cmhse_contrastive_blocks_fwd(const float* im, const float* s,
   p.blk_stride = static_cast<int64_t>(max_n) * max_n;
   const unsigned tiles = static_cast<unsigned>(p.n_tiles) * ((max_n + bt - 1) / bt);
   const size_t smem = small ? TileSmem<64, 64>::kBytes : TileSmem<kSimBM, kSimBN>::kBytes;
-  if (small && D % 4 == 0)
-    hipLaunchKernelGGL((sim_kernel<kSimStore, true, 1>), dim3(tiles, n_blocks), dim3(kThreads), smem,
-                       stream, p);
-  else if (small)
-    hipLaunchKernelGGL((sim_kernel<kSimStore, false, 1>), dim3(tiles, n_blocks), dim3(kThreads), smem,
-                       stream, p);
-  else if (D % 4 == 0)
-    hipLaunchKernelGGL((sim_kernel<kSimStore, true>), dim3(tiles, n_blocks), dim3(kThreads), smem,
-                       stream, p);
-  else
-    hipLaunchKernelGGL((sim_kernel<kSimStore, false>), dim3(tiles, n_blocks), dim3(kThreads), smem,
-                       stream, p);
+  const dim3 grid(tiles, n_blocks);
+  const int rc =
+      small ? launch_tiles(sim_kernel<kSimStore, true, 1>, sim_kernel<kSimStore, false, 1>, D, grid, smem, stream, p)
+            : launch_tiles(sim_kernel<kSimStore, true>, sim_kernel<kSimStore, false>, D, grid, smem, stream, p);
+  if (rc != CMHSE_OK) return rc;
   LossParams lp;
   lp.scores = p.scores;
   lp.n = max_n;
@@ -577,7 +518,7 @@ extern "C" int cmhse_contrastive_blocks_fwd(const float* im, const float* s,
   lp.norm = norm;
   lp.partial = reinterpret_cast<double*>(
       static_cast<char*>(workspace) +
-      align_up_(static_cast<size_t>(n_blocks) * max_n * max_n * sizeof(float), 256));
+      align256(static_cast<size_t>(n_blocks) * max_n * max_n * sizeof(float)));
   lp.loss = losses;
   lp.blk_off = blk_off;
   lp.blk_stride = p.blk_stride;
@@ -748,8 +689,8 @@ extern "C" int cmhse_step_losses_fwd(const cmhse_step_losses* d, float* values, 
 extern "C" size_t cmhse_groupwise_workspace(int32_t n, int32_t B) {
   if (n <= 0 || B <= 0) return 0;
   const size_t nrb = (B + 63) / 64;
-  return align_up_(static_cast<size_t>(n) * n * sizeof(float), 256) +
-         align_up_(2 * nrb * sizeof(double), 256);
+  return align256(static_cast<size_t>(n) * n * sizeof(float)) +
+         align256(2 * nrb * sizeof(double));
 }
 
 extern "C" int cmhse_groupwise_fwd(const float* im, const float* s, int32_t n, int32_t D,
@@ -779,7 +720,7 @@ extern "C" int cmhse_groupwise_fwd(const float* im, const float* s, int32_t n, i
   lp.max_violation = max_violation;
   lp.norm = norm;
   lp.partial = reinterpret_cast<double*>(static_cast<char*>(workspace) +
-                                         align_up_(static_cast<size_t>(n) * n * sizeof(float), 256));
+                                         align256(static_cast<size_t>(n) * n * sizeof(float)));
   lp.loss = loss;
   lp.blk_off = nullptr;
   lp.blk_stride = 0;

@@ -1,9 +1,8 @@
 // topk.hip — cmhse_sim_topk: the K best gallery columns of every query row, matrix-free.
 //
 // For the stripe [row0, row0 + nrows) of A [N, D] against B [M, D], d[i, j] = A[i] . B[j]: the K
-// columns with the largest d, by score descending and then column ascending on exact ties.  The
-// order is that of the 64-bit key (ordered_bits(d) << 32) | (0xFFFFFFFF - j), the key sim.hip's top-1
-// already keeps: unique per row, so the result depends on neither tiling nor scheduling.
+// columns with the largest d, by score descending and then column ascending on exact ties: the order
+// of the score key of score_tile.hpp, which also decides sim_rank's top-1.
 //
 // Bit-exactness: every d[i, j] comes out of nt_phase (nt_core.hpp), whose k order per output does
 // not depend on the tile shape or position — the scores returned are bit-identical to
@@ -25,11 +24,10 @@
 
 #include "../../include/cmhse_hip.h"
 #include "nt_core.hpp"
+#include "score_tile.hpp"
 
 namespace cmhse {
 namespace {
-
-typedef unsigned long long tkey_t;
 
 constexpr int kTkBM = 64;                 // query rows per workgroup
 constexpr int kTkBN = 128;                // gallery columns per tile
@@ -40,36 +38,25 @@ constexpr size_t kTkLdsPerCU = 160 * 1024;
 constexpr size_t kTkTileBytes =
     (TileSmem<kTkBM, kTkBN>::kBytes > sizeof(float) * kTkBM * kTkLd) ? TileSmem<kTkBM, kTkBN>::kBytes
                                                                        : sizeof(float) * kTkBM * kTkLd;
-constexpr size_t kTkCandBytes = sizeof(tkey_t) * kTkBN * (kThreads / 64);   // one buffer per wave
+constexpr size_t kTkCandBytes = sizeof(score_key_t) * kTkBN * (kThreads / 64);   // one buffer per wave
 
 struct TopkParams {
-  const float* A;  // [N, D]
-  const float* B;  // [M, D]
+  const float* A;    // [N, D]
+  const float* B;    // [M, D]
   int32_t M, D, row0, nrows, K;
   int32_t row_tiles, col_tiles, panels;
-  tkey_t* ws;      // [panels, nrows, K] sorted keys of each panel
-  float* scores;   // [nrows, K]
-  int32_t* index;  // [nrows, K]
+  score_key_t* ws;   // [panels, nrows, K] sorted keys of each panel
+  float* scores;     // [nrows, K]
+  int32_t* index;    // [nrows, K]
 };
-
-__device__ __forceinline__ tkey_t score_key(float v, int j) {
-  const unsigned u = __float_as_uint(v);
-  const unsigned ob = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // monotone float -> uint32
-  return (static_cast<tkey_t>(ob) << 32) | static_cast<tkey_t>(0xFFFFFFFFu - static_cast<unsigned>(j));
-}
-
-__device__ __forceinline__ float key_score(tkey_t key) {
-  const unsigned ob = static_cast<unsigned>(key >> 32);
-  return __uint_as_float((ob & 0x80000000u) ? (ob & 0x7FFFFFFFu) : ~ob);
-}
 
 // One wave merges c candidate keys (cand[0, c), unsorted, c <= 128, all above lst[K - 1]) into the
 // descending list lst[0, K) (0 = empty slot; a real key is never 0).  Keys are unique, so each one's
 // place in the merged order is its rank: a list entry moves down by the candidates above it, a
 // candidate lands at (list entries above it) + (candidates above it); what lands past K drops out.
 // Every lane has read all it needs before any lane writes (lock-step wave, in-order LDS).
-__device__ __forceinline__ void wave_merge(tkey_t* lst, int K, const tkey_t* cand, int c, int lane) {
-  tkey_t lv[2], cv[2];
+__device__ __forceinline__ void wave_merge(score_key_t* lst, int K, const score_key_t* cand, int c, int lane) {
+  score_key_t lv[2], cv[2];
   int lr[2] = {0, 0}, cr[2] = {0, 0};
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -78,7 +65,7 @@ __device__ __forceinline__ void wave_merge(tkey_t* lst, int K, const tkey_t* can
     cv[h] = e < c ? cand[e] : 0ull;
   }
   for (int q = 0; q < c; ++q) {
-    const tkey_t x = cand[q];   // (one address for the whole wave: a broadcast read)
+    const score_key_t x = cand[q];   // (one address for the whole wave: a broadcast read)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       lr[h] += x > lv[h];
@@ -122,27 +109,23 @@ __global__ __launch_bounds__(kThreads) void topk_select_kernel(const TopkParams 
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* stage = smem;   // nt_phase's tile buffers, then the tile's scores [kTkBM][kTkLd]
-  tkey_t* lists = reinterpret_cast<tkey_t*>(reinterpret_cast<char*>(smem) + kTkTileBytes);   // [kTkBM][K]
+  score_key_t* lists =
+      reinterpret_cast<score_key_t*>(reinterpret_cast<char*>(smem) + kTkTileBytes);   // [kTkBM][K]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, srow = tid >> 2;
-  tkey_t* cand = lists + kTkBM * K + wave * kTkBN;
+  score_key_t* cand = lists + kTkBM * K + wave * kTkBN;
   for (int e = tid; e < kTkBM * K; e += kThreads) lists[e] = 0ull;   // (seen after nt_phase's barriers)
 
   rowaddr_t ar[1];
   bool av[1];
-  av[0] = i0 + srow < p.nrows;
-  ar[0] = row_addr(p.A + static_cast<int64_t>(p.row0 + (av[0] ? i0 + srow : 0)) * p.D);
+  ar[0] = tile_row(p.A, p.D, p.row0, i0 + srow, p.nrows, &av[0]);
   const int b_row0[2] = {wn * 64, wn * 64 + 32};
   for (int t = t_begin; t < t_end; ++t) {
     const int j0 = t * kTkBN;
     rowaddr_t br[2];
     bool bv[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int j = j0 + srow + 64 * i;
-      bv[i] = j < p.M;
-      br[i] = row_addr(p.B + static_cast<int64_t>(bv[i] ? j : 0) * p.D);
-    }
+    for (int i = 0; i < 2; ++i) br[i] = tile_row(p.B, p.D, 0, j0 + srow + 64 * i, p.M, &bv[i]);
     f32x16 acc[1][2] = {{zero16(), zero16()}};
     // starts with a barrier (every wave is done with the previous tile's staged scores) and ends
     // with one (every wave has read its last fragments)
@@ -156,12 +139,12 @@ __global__ __launch_bounds__(kThreads) void topk_select_kernel(const TopkParams 
     for (int rr = 0; rr < kTkBM / 4; ++rr) {
       const int row = wave * (kTkBM / 4) + rr;
       if (i0 + row >= p.nrows) break;   // (wave-uniform)
-      tkey_t* lst = lists + row * K;
-      const tkey_t thr = lst[K - 1];
+      score_key_t* lst = lists + row * K;
+      const score_key_t thr = lst[K - 1];
       const float* srow_scores = stage + row * kTkLd;
       // columns past M (and rows past the tile's edge) hold garbage: key 0 never beats a threshold
-      const tkey_t k0 = (j0 + lane < p.M) ? score_key(srow_scores[lane], j0 + lane) : 0ull;
-      const tkey_t k1 = (j0 + 64 + lane < p.M) ? score_key(srow_scores[64 + lane], j0 + 64 + lane) : 0ull;
+      const score_key_t k0 = (j0 + lane < p.M) ? score_key(srow_scores[lane], j0 + lane) : 0ull;
+      const score_key_t k1 = (j0 + 64 + lane < p.M) ? score_key(srow_scores[64 + lane], j0 + 64 + lane) : 0ull;
       const bool c0 = k0 > thr, c1 = k1 > thr;
       const unsigned long long m0 = __ballot(c0), m1 = __ballot(c1);
       if ((m0 | m1) == 0ull) continue;
@@ -174,27 +157,27 @@ __global__ __launch_bounds__(kThreads) void topk_select_kernel(const TopkParams 
   }
   __syncthreads();
   const int rows = (p.nrows - i0 < kTkBM) ? p.nrows - i0 : kTkBM;
-  tkey_t* out = p.ws + (static_cast<int64_t>(panel) * p.nrows + i0) * K;
+  score_key_t* out = p.ws + (static_cast<int64_t>(panel) * p.nrows + i0) * K;
   for (int e = tid; e < rows * K; e += kThreads) out[e] = lists[e];
 }
 
 // One wave per row: the P panel lists (each sorted: its candidates are a prefix) into one, decoded.
 __global__ __launch_bounds__(kThreads) void topk_merge_kernel(const TopkParams p) {
-  __shared__ tkey_t s_list[kThreads / 64][CMHSE_TOPK_MAX];
-  __shared__ tkey_t s_cand[kThreads / 64][CMHSE_TOPK_MAX];
+  __shared__ score_key_t s_list[kThreads / 64][CMHSE_TOPK_MAX];
+  __shared__ score_key_t s_cand[kThreads / 64][CMHSE_TOPK_MAX];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = blockIdx.x * (kThreads / 64) + wave;
   if (li >= p.nrows) return;   // (no barrier below)
   const int K = p.K;
-  tkey_t* lst = s_list[wave];
-  tkey_t* cand = s_cand[wave];
+  score_key_t* lst = s_list[wave];
+  score_key_t* cand = s_cand[wave];
   for (int e = lane; e < K; e += 64) lst[e] = 0ull;
   __builtin_amdgcn_wave_barrier();
   for (int q = 0; q < p.panels; ++q) {
-    const tkey_t* src = p.ws + (static_cast<int64_t>(q) * p.nrows + li) * K;
-    const tkey_t thr = lst[K - 1];
-    const tkey_t k0 = lane < K ? src[lane] : 0ull;
-    const tkey_t k1 = lane + 64 < K ? src[lane + 64] : 0ull;
+    const score_key_t* src = p.ws + (static_cast<int64_t>(q) * p.nrows + li) * K;
+    const score_key_t thr = lst[K - 1];
+    const score_key_t k0 = lane < K ? src[lane] : 0ull;
+    const score_key_t k1 = lane + 64 < K ? src[lane + 64] : 0ull;
     const bool c0 = k0 > thr, c1 = k1 > thr;
     const int c = __popcll(__ballot(c0)) + __popcll(__ballot(c1));
     if (c == 0) continue;
@@ -204,15 +187,14 @@ __global__ __launch_bounds__(kThreads) void topk_merge_kernel(const TopkParams p
     wave_merge(lst, K, cand, c, lane);
   }
   for (int e = lane; e < K; e += 64) {
-    const tkey_t key = lst[e];
+    const score_key_t key = lst[e];
     p.scores[static_cast<int64_t>(li) * K + e] = key_score(key);
-    p.index[static_cast<int64_t>(li) * K + e] =
-        static_cast<int32_t>(0xFFFFFFFFu - static_cast<unsigned>(key & 0xFFFFFFFFull));
+    p.index[static_cast<int64_t>(li) * K + e] = key_index(key);
   }
 }
 
 size_t topk_smem(int K) {
-  return kTkTileBytes + sizeof(tkey_t) * kTkBM * static_cast<size_t>(K) + kTkCandBytes;
+  return kTkTileBytes + sizeof(score_key_t) * kTkBM * static_cast<size_t>(K) + kTkCandBytes;
 }
 
 // Panels per row tile: as many as fill every CU's resident workgroups ONCE (LDS decides how many fit),
@@ -227,8 +209,6 @@ int topk_panels(int nrows, int M, int K) {
   return P < 1 ? 1 : P;
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 }  // namespace cmhse
 
@@ -237,7 +217,7 @@ using namespace cmhse;
 extern "C" size_t cmhse_sim_topk_workspace(int32_t nrows, int32_t M, int32_t K) {
   if (nrows <= 0 || M <= 0 || K < 1 || K > CMHSE_TOPK_MAX) return 0;
   return align256(static_cast<size_t>(topk_panels(nrows, M, K)) * static_cast<size_t>(nrows) *
-                  static_cast<size_t>(K) * sizeof(tkey_t));
+                  static_cast<size_t>(K) * sizeof(score_key_t));
 }
 
 extern "C" int cmhse_sim_topk(const float* A, const float* B, int32_t N, int32_t M, int32_t D,
@@ -264,24 +244,15 @@ extern "C" int cmhse_sim_topk(const float* A, const float* B, int32_t N, int32_t
   p.row_tiles = (nrows + kTkBM - 1) / kTkBM;
   p.col_tiles = (M + kTkBN - 1) / kTkBN;
   p.panels = topk_panels(nrows, M, K);
-  p.ws = static_cast<tkey_t*>(workspace);
+  p.ws = static_cast<score_key_t*>(workspace);
   p.scores = scores;
   p.index = index;
   const int64_t blocks = (static_cast<int64_t>(p.row_tiles) * p.panels + 7) / 8 * 8;
   if (blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
-  const size_t smem = topk_smem(K);
-  const void* fn = (D % 4 == 0) ? reinterpret_cast<const void*>(&topk_select_kernel<true>)
-                                : reinterpret_cast<const void*>(&topk_select_kernel<false>);
-  // past the 64 KiB a launch may ask for by default (K > 52); per device, host-side, no synchronisation
-  if (smem > 64 * 1024 &&
-      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
-    return CMHSE_ERR_LAUNCH;
-  if (D % 4 == 0)
-    hipLaunchKernelGGL(topk_select_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), smem,
-                       stream, p);
-  else
-    hipLaunchKernelGGL(topk_select_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), smem,
-                       stream, p);
+  // (past 64 KiB of LDS for K > 52)
+  const int rc = launch_tiles(topk_select_kernel<true>, topk_select_kernel<false>, D,
+                              dim3(static_cast<unsigned>(blocks)), topk_smem(K), stream, p);
+  if (rc != CMHSE_OK) return rc;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((nrows + 3) / 4), dim3(kThreads), 0, stream, p);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }

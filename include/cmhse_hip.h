@@ -340,6 +340,7 @@ int cmhse_sim_topk(const float* A, const float* B, int32_t N, int32_t M, int32_t
 #define CMHSE_GROUP_MEAN 0
 #define CMHSE_GROUP_MAX 1
 #define CMHSE_GROUP_PLAN_MAX(B) (4 * (B) + 9)
+#define CMHSE_GROUP_TILE_ROWS 128   /* the most clip / caption rows of a tile, so of a video / paragraph */
 int32_t cmhse_group_plan(const int32_t* clip_off_host, const int32_t* cap_off_host, int32_t B,
                          int32_t* plan, int32_t plan_cap);
 int cmhse_group_scores(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,

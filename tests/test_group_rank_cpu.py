@@ -114,6 +114,7 @@ def test_plan_max_matches_header():
   assert '#define CMHSE_GROUP_PLAN_MAX(B) (4 * (B) + 9)' in header
   assert '#define CMHSE_GROUP_MAX %d' % _lib.GROUP_MAX in header
   assert '#define CMHSE_GROUP_MEAN %d' % _lib.GROUP_MEAN in header
+  assert '#define CMHSE_GROUP_TILE_ROWS %d' % _lib.GROUP_TILE_ROWS in header
   assert _lib.group_plan_max(10) == 49
 
 
