@@ -579,21 +579,28 @@ static void bwd_tail(BwdJob& j) {
   j.tail_lo = lo;
 }
 
+// The kernel of a BPTT step: none (no step in this launch), gru_bwd_step_kernel's 32 x 32 tile with
+// 4 or 8 waves, gru_bwd_step_mid_kernel's 16- or 32-row tile, or the split step (bwd_rec_part_kernel
+// and bwd_gates_kernel, two launches of its own).
+enum class BwdStep { None, Waves4, Waves8, Mid16, Mid32, Split };
+
 // Phase 2: BPTT of all jobs, last step first.  Launch i serves step Tmax_k - 1 - i of every job k
-// that still has one (and the extra t = -1 launch of a job that wants d h0); jobs of equal block
-// size share the launch.
+// that still has one (and the extra t = -1 launch of a job that wants d h0); jobs of equal step
+// shape share the launch.
 void bwd_steps(BwdJob* jobs, int n) {
   constexpr int nw8_max = kBwdNw8Max;
   int longest = 0;
   for (int k = 0; k < n; ++k) longest = jobs[k].b->Tmax > longest ? jobs[k].b->Tmax : longest;
   for (int i = 0; i <= longest; ++i) {
-    int kind[CMHSE_MAX_JOBS];      // 0 = not in this launch, 1 = 4 waves, 2 = 8 waves, +4 = scalar loads; 8 | shape bits = gru_bwd_step_mid_kernel
+    BwdStep shape[CMHSE_MAX_JOBS];
+    bool vec[CMHSE_MAX_JOBS];      // Waves4 / Waves8: dwordx4 loads (H % 4 == 0), else the scalar-load variant
     unsigned grid_k[CMHSE_MAX_JOBS];
     for (int k = 0; k < n; ++k) {
       BwdJob& j = jobs[k];
       const cmhse_seq_batch* b = j.b;
       const int t = b->Tmax - 1 - i;
-      kind[k] = 0;
+      shape[k] = BwdStep::None;
+      vec[k] = b->H % 4 == 0;
       if (t < -1 || (t < 0 && !j.dh0)) continue;
       const int S_t = (t >= 0) ? b->step_count_host[t] : b->S;
       const int S_next = (t + 1 < b->Tmax) ? b->step_count_host[t + 1] : 0;
@@ -605,21 +612,21 @@ void bwd_steps(BwdJob* jobs, int n) {
       sp.off_cur = j.off;
       sp.off_prev = (t > 0) ? j.off - b->step_count_host[t - 1] : 0;
       if (i == 0) bwd_tail(j);                 // the chain's few-sequence tail, if it has one: one kernel
-      if (j.tail_lo >= 0 && t >= j.tail_lo) continue;   // (kind 0) the resident kernel does this step
+      if (j.tail_lo >= 0 && t >= j.tail_lo) continue;   // (None) the resident kernel does this step
       grid_k[k] = static_cast<unsigned>((b->H + 31) / 32) * ((S_t + 31) / 32);
       // few active sequences: a pure latency chain on an under-filled chip -> 8 waves split K
-      kind[k] = ((S_t <= nw8_max) ? 2 : 1) | ((b->H % 4 == 0) ? 0 : 4);
-      if (b->H % 4 == 0 && S_t <= bwd_mid_max_seqs()) {   // the 16 x 16 x 4 tile shapes
+      shape[k] = (S_t <= nw8_max) ? BwdStep::Waves8 : BwdStep::Waves4;
+      if (vec[k] && S_t <= bwd_mid_max_seqs()) {   // the 16 x 16 x 4 tile shapes
         const int bm = (S_t <= 16) ? 16 : 32;
         const int bu = kBwdMidUnits;
-        kind[k] = 8 | (bm == 16 ? 16 : 0);
+        shape[k] = (bm == 16) ? BwdStep::Mid16 : BwdStep::Mid32;
         grid_k[k] = static_cast<unsigned>((b->H + bu - 1) / bu) * ((S_t + bm - 1) / bm);
         const int split_min = tunables().bwd_split_min_seqs.load(std::memory_order_relaxed);
-        if (split_min > 0 && S_t >= split_min) kind[k] = 32;   // two launches, a third of the bytes
+        if (split_min > 0 && S_t >= split_min) shape[k] = BwdStep::Split;   // two launches, a third of the bytes
       }
     }
     for (int k = 0; k < n; ++k) {
-      if (kind[k] != 32) continue;
+      if (shape[k] != BwdStep::Split) continue;
       BwdJob& j = jobs[k];
       const BwdStepParams& sp = j.sp;
       const int H = sp.H, K = 3 * H;
@@ -644,40 +651,33 @@ void bwd_steps(BwdJob* jobs, int n) {
       const int64_t elems = static_cast<int64_t>(sp.S_t) * (H / 4);
       hipLaunchKernelGGL(bwd_gates_kernel, dim3(static_cast<unsigned>((elems + kThreads - 1) / kThreads)),
                          dim3(kThreads), 0, j.st, gp);
-      kind[k] = 0;
+      shape[k] = BwdStep::None;
     }
     for (int k = 0; k < n; ++k) {
-      if (kind[k] == 0) continue;
+      if (shape[k] == BwdStep::None) continue;
       BwdStepGroup g;
       g.n = 0;
       unsigned grid = 0;
-      const int kd = kind[k];
+      const BwdStep sd = shape[k];
+      const bool vd = vec[k];
       hipStream_t st = jobs[k].st;
       for (int m = k; m < n; ++m) {
-        if (kind[m] != kd || jobs[m].st != st) continue;   // same kernel, same stream: one launch
+        if (shape[m] != sd || vec[m] != vd || jobs[m].st != st) continue;   // same kernel, same stream: one launch
         g.j[g.n] = jobs[m].sp;
         g.start[g.n] = grid;
         grid += grid_k[m];
         ++g.n;
-        kind[m] = 0;
+        shape[m] = BwdStep::None;
       }
       for (int m = g.n; m < CMHSE_MAX_JOBS; ++m) g.start[m] = 0xffffffffu;
-      const bool vec = (kd & 4) == 0;
-      if ((kd & 8) != 0) {
-        if ((kd & 16) != 0)
-          hipLaunchKernelGGL((gru_bwd_step_mid_kernel<1, kBwdMidUnits>), dim3(grid), dim3(64 * kBwdMidNW), 0, st, g);
-        else
-          hipLaunchKernelGGL((gru_bwd_step_mid_kernel<2, kBwdMidUnits>), dim3(grid), dim3(64 * kBwdMidNW), 0, st, g);
-      } else if ((kd & 3) == 2) {
-        if (vec)
-          hipLaunchKernelGGL((gru_bwd_step_kernel<true, 8>), dim3(grid), dim3(512), 0, st, g);
-        else
-          hipLaunchKernelGGL((gru_bwd_step_kernel<false, 8>), dim3(grid), dim3(512), 0, st, g);
-      } else if (vec) {
-        hipLaunchKernelGGL((gru_bwd_step_kernel<true, 4>), dim3(grid), dim3(kThreads), 0, st, g);
-      } else {
-        hipLaunchKernelGGL((gru_bwd_step_kernel<false, 4>), dim3(grid), dim3(kThreads), 0, st, g);
-      }
+      if (sd == BwdStep::Mid16)
+        hipLaunchKernelGGL((gru_bwd_step_mid_kernel<1, kBwdMidUnits>), dim3(grid), dim3(64 * kBwdMidNW), 0, st, g);
+      else if (sd == BwdStep::Mid32)
+        hipLaunchKernelGGL((gru_bwd_step_mid_kernel<2, kBwdMidUnits>), dim3(grid), dim3(64 * kBwdMidNW), 0, st, g);
+      else if (sd == BwdStep::Waves8)
+        hipLaunchKernelGGL((vd ? gru_bwd_step_kernel<true, 8> : gru_bwd_step_kernel<false, 8>), dim3(grid), dim3(512), 0, st, g);
+      else
+        hipLaunchKernelGGL((vd ? gru_bwd_step_kernel<true, 4> : gru_bwd_step_kernel<false, 4>), dim3(grid), dim3(kThreads), 0, st, g);
     }
     // weight gradients of the rows this launch completed, beside the rest of the chain: a chunk
     // closes when it spans bwd_chunk_rows rows, and at step 0

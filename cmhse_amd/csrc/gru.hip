@@ -425,8 +425,6 @@ int prepare_job(const cmhse_seq_batch* b, const cmhse_gru_weights* w, int32_t po
   return CMHSE_OK;
 }
 
-// Which step kernel serves job `j` at its current step: 0 = tiny, 1 = tiled fp32, 2 = tiled bf16x3;
-// bit 2 = scalar-load variant.  Jobs of equal kind share a launch.
 // Hidden units per workgroup of the mid-size step: the narrowest of 16, 8, 4 whose grid still
 // fits the chip in one round (more, smaller tiles = more CUs pulling operands; past one round the
 // replicated h rows cost more than the spread gains).  Tunables::mid_units = 16 | 8 | 4 forces one.
@@ -440,14 +438,35 @@ static int mid_units(int H, int m_blocks) {
   return 16;
 }
 
+// The shape of a forward step launch: its kernel family, and the workgroup tile of `rows` active
+// sequences x `units` hidden units that `waves` waves compute.
+//   Tiny      gru_step_tiny_kernel          kTinyBM x kTinyBU, 4 waves (the latency-shaped exact-fp32 step)
+//   Tiled     gru_step_kernel               64 | 128 x kGruBU, 4 waves (also the step chain's tile)
+//   TiledBf3  gru_step_kernel (bf16x3 ring) 128 x kGruBU, 4 waves
+//   Mid       gru_step_mid_kernel           16 | 32 | 64 x 16 | 8 | 4, 4 | 8 waves (64 rows: 16 units, 8 waves)
+// `vec`: dwordx4 operand loads, else the scalar-load variant (TiledBf3 and Mid: vec jobs only).
+// Requests of equal shape on one stream share a launch; step_kernel() maps a shape to its kernel.
+struct StepShape {
+  enum Family { Tiny, Tiled, TiledBf3, Mid } family;
+  bool vec;
+  int rows, units, waves;
+  bool operator==(const StepShape& o) const {
+    return family == o.family && vec == o.vec && rows == o.rows && units == o.units && waves == o.waves;
+  }
+  bool operator!=(const StepShape& o) const { return !(*this == o); }
+  bool tiled() const { return family == Tiled || family == TiledBf3; }
+  int row_tiles(int S_t) const { return (S_t + rows - 1) / rows; }
+  unsigned grid(int H, int S_t) const { return static_cast<unsigned>((H + units - 1) / units) * row_tiles(S_t); }
+};
+
 // `mid_blocks`: 16/32-sequence blocks of ALL requests of the call that run a mid-size step at this
 // time step (they share the chip, and a launch when their shapes agree).  `alone`: nothing else of
 // the call competes for workgroup slots at this step (no LDS-tiled step, no chain moved to the
-// side stream, no attention pass started beside the steps) — the 8-wave shape is used (bit 512);
-// it and the 4-wave shape compute bit-identical results (kMidSlices).
+// side stream, no attention pass started beside the steps) — the 8-wave shape is used; it and the
+// 4-wave shape compute bit-identical results (kMidSlices).
 // `tiled_wgs`: 64-row workgroups of all requests that run an fp32 LDS-tiled step at this time step
-// (bit 2048 = 128-row tiles, gru_msub_for()).
-int step_kind(const FwdJob& j, int S_t, int mid_blocks, bool alone, int tiled_wgs) {
+// (128-row tiles: gru_msub_for()).
+StepShape step_shape(const FwdJob& j, int S_t, int mid_blocks, bool alone, int tiled_wgs) {
   if (j.p.t >= j.t_mid) {   // mid-size kernel (vec shapes only)
     const int waves = tunables().mid_waves.load(std::memory_order_relaxed);   // 4 | 8 forces a shape
     if (waves == 4) alone = false;
@@ -458,152 +477,105 @@ int step_kind(const FwdJob& j, int S_t, int mid_blocks, bool alone, int tiled_wg
     const int tall = tunables().mid_tall_min_seqs.load(std::memory_order_relaxed);
     // (a 48-sequence tile for 129-192 sequences — one round of 192 / 256 workgroups instead of 192 of
     // this shape — was built in round 4, bit-identical, and changed nothing: profiles/r04_train_ab.txt)
-    if (tall > 0 && S_t >= tall && bu == 16 && alone && j.save) return 3 | 512 | 8192;   // (training calls: the validation pass keeps its shapes)
-    return 3 | (S_t <= 16 ? 32 : 0) | (bu == 8 ? 128 : 0) | (bu == 4 ? 256 : 0) |
-           (alone ? 512 : 0);
+    if (tall > 0 && S_t >= tall && bu == 16 && alone && j.save)   // (training calls: the validation pass keeps its shapes)
+      return {StepShape::Mid, j.vec, 64, 16, 8};
+    return {StepShape::Mid, j.vec, S_t <= 16 ? 16 : 32, bu, alone ? 8 : 4};
   }
   // (WHICH of the differently-ordered sums serves the step comes from kind_count — the whole
   // split's active count when the batch is a share of one — so that a sequence sees the same
-  // arithmetic whatever else is in its batch; shapes within a kind are bit-identical)
-  int k = (j.kind_count[j.p.t] <= tiny_max_seqs()) ? 0 : (j.bf3 ? 2 : 1);
-  if (k == 1 && gru_msub_for(tiled_wgs) == 2) k |= 2048;
-  return k | (j.vec ? 0 : 4);
+  // arithmetic whatever else is in its batch; shapes within a family are bit-identical)
+  if (j.kind_count[j.p.t] <= tiny_max_seqs()) return {StepShape::Tiny, j.vec, kTinyBM, kTinyBU, 4};
+  // bf16x3: a staging-bound loop, the 128-row tile halves the weight bytes per MFMA
+  if (j.bf3) return {StepShape::TiledBf3, j.vec, 128, kGruBU, 4};
+  return {StepShape::Tiled, j.vec, gru_msub_for(tiled_wgs) == 2 ? 128 : 64, kGruBU, 4};
+}
+
+// The kernel instantiations and dynamic LDS of a shape (its block is 64 x waves threads).
+using StepFn = void (*)(GruStepGroup);
+struct StepKernel {
+  StepFn step;
+  void (*chain)(GruChainGroup);   // Tiled: the step chain's kernel of the same tile
+  size_t smem;
+};
+
+template <int MB>
+static StepFn mid_kernel(int units, int waves) {
+  if (units == 4) return waves == 8 ? gru_step_mid_kernel<MB, 4, 8> : gru_step_mid_kernel<MB, 4, 4>;
+  if (units == 8) return waves == 8 ? gru_step_mid_kernel<MB, 8, 8> : gru_step_mid_kernel<MB, 8, 4>;
+  return waves == 8 ? gru_step_mid_kernel<MB, 16, 8> : gru_step_mid_kernel<MB, 16, 4>;
+}
+
+static StepKernel step_kernel(const StepShape& s) {
+  constexpr size_t tile64 = TileSmem<64, 3 * kGruBU>::kBytes, tile128 = TileSmem<128, 3 * kGruBU>::kBytes;
+  switch (s.family) {
+    case StepShape::Tiny:
+      return {s.vec ? gru_step_tiny_kernel<true, 4> : gru_step_tiny_kernel<false, 4>, nullptr, 0};
+    case StepShape::TiledBf3:
+      return {gru_step_kernel<true, 2, true>, nullptr, RingSmem<128, 3 * kGruBU>::kBytes};
+    case StepShape::Mid:
+      if (s.rows == 64) return {gru_step_mid_kernel<4, 16, 8>, nullptr, 0};
+      return {s.rows == 16 ? mid_kernel<1>(s.units, s.waves) : mid_kernel<2>(s.units, s.waves), nullptr, 0};
+    default:
+      if (s.rows == 128)
+        return s.vec ? StepKernel{gru_step_kernel<true, 2, false>, gru_step_chain_kernel<true, 2>, tile128}
+                     : StepKernel{gru_step_kernel<false, 2, false>, gru_step_chain_kernel<false, 2>, tile128};
+      return s.vec ? StepKernel{gru_step_kernel<true, 1, false>, gru_step_chain_kernel<true, 1>, tile64}
+                   : StepKernel{gru_step_kernel<false, 1, false>, gru_step_chain_kernel<false, 1>, tile64};
+  }
+}
+
+void launch_group(const GruStepGroup& g, const StepShape& s, unsigned grid, hipStream_t stream) {
+  const StepKernel k = step_kernel(s);
+  hipLaunchKernelGGL(k.step, dim3(grid), dim3(64 * s.waves), k.smem, stream, g);
+}
+
+// xproj_kernel over rows [q.m_begin, q.rows) of q, the fields both projections share taken from job j
+static void launch_xproj_kernel(const FwdJob& j, XprojParams q, hipStream_t stream) {
+  q.emb = j.b->emb_table;
+  q.w_ih = j.w->w_ih;
+  q.I = j.b->I;
+  q.N = 3 * j.b->H;
+  q.vocab = j.b->vocab;
+  q.n_tiles = (q.N + 191) / 192;
+  const int64_t grid = static_cast<int64_t>(q.n_tiles) * ((q.rows - q.m_begin + 63) / 64);
+  if (grid <= 0) return;
+  hipLaunchKernelGGL(xproj_kernel, dim3(static_cast<unsigned>(grid)), dim3(kThreads), (TileSmem<64, 192>::kBytes),
+                     stream, q);
 }
 
 // The input projection of the steps >= t_mid of a job: gx rows [m_begin, m_end) (relative to the
 // first hoisted row; m_end < 0 = all of them).
 void launch_xproj(const FwdJob& j, hipStream_t stream, int64_t m_begin = 0, int64_t m_end = -1) {
   const cmhse_seq_batch* b = j.b;
-  const int t_first = j.t_mid;
-  XprojParams q;
+  XprojParams q{};
   q.x_rows = b->x_rows;
   q.tok_rows = b->tok_rows;
-  q.emb = b->emb_table;
   q.step_off = b->step_off;
-  q.w_ih = j.w->w_ih;
   q.gx = const_cast<float*>(j.p.gx);
   q.p0 = j.p.gx_p0;
   q.per_seq = j.p.gx_per_seq;
-  q.rows = q.per_seq ? b->step_count_host[t_first] : (j.sum_T - j.p.gx_p0);
+  q.rows = q.per_seq ? b->step_count_host[j.t_mid] : (j.sum_T - j.p.gx_p0);
   if (m_end >= 0 && m_end < q.rows) q.rows = m_end;
   q.m_begin = m_begin;
-  q.I = b->I;
-  q.N = 3 * b->H;
-  q.vocab = b->vocab;
   q.x_step = b->x_step_floats;
   q.Tmax = b->Tmax;
-  q.t_first = t_first;
-  q.n_tiles = (q.N + 191) / 192;
-  q.vocab_rows = 0;
-  const int64_t grid = static_cast<int64_t>(q.n_tiles) * ((q.rows - q.m_begin + 63) / 64);
-  if (grid <= 0) return;
-  const size_t smem = TileSmem<64, 192>::kBytes;
-  hipLaunchKernelGGL(xproj_kernel, dim3(static_cast<unsigned>(grid)), dim3(kThreads), smem, stream, q);
+  q.t_first = j.t_mid;
+  launch_xproj_kernel(j, q, stream);
 }
 
 // The token projection table of job j: G[v] = emb[v] W_ih^T for every token id v — the x-phase
 // accumulators a tile computes for token v (xproj_kernel has the step tile's shape and k order).
 void launch_tok_table(const FwdJob& j, hipStream_t stream) {
-  const cmhse_seq_batch* b = j.b;
-  XprojParams q;
-  q.x_rows = nullptr;
-  q.tok_rows = nullptr;
-  q.emb = b->emb_table;
-  q.step_off = nullptr;
-  q.w_ih = j.w->w_ih;
+  XprojParams q{};
   q.gx = const_cast<float*>(j.p.tok_tab);
-  q.p0 = 0;
-  q.rows = b->vocab;
-  q.m_begin = 0;
-  q.I = b->I;
-  q.N = 3 * b->H;
-  q.vocab = b->vocab;
-  q.x_step = 0;
-  q.Tmax = 0;
-  q.t_first = 0;
-  q.per_seq = 0;
+  q.rows = j.b->vocab;
   q.vocab_rows = 1;
-  q.n_tiles = (q.N + 191) / 192;
-  const int64_t grid = static_cast<int64_t>(q.n_tiles) * ((q.rows + 63) / 64);
-  const size_t smem = TileSmem<64, 192>::kBytes;
-  hipLaunchKernelGGL(xproj_kernel, dim3(static_cast<unsigned>(grid)), dim3(kThreads), smem, stream, q);
+  launch_xproj_kernel(j, q, stream);
 }
 
-void launch_group(const GruStepGroup& g, int kind, unsigned grid, hipStream_t stream) {
-  const bool vec = (kind & 4) == 0;
-  const int msub = (kind & 2048) != 0 ? 2 : 1;
-  switch (kind & 3) {
-    case 3: {
-      const int bu = (kind & 256) != 0 ? 4 : ((kind & 128) != 0 ? 8 : 16);
-#define MID_LAUNCH_(MB, BU)                                                                      \
-  do {                                                                                                \
-    if ((kind & 512) != 0)                                                                            \
-      hipLaunchKernelGGL((gru_step_mid_kernel<MB, BU, 8>), dim3(grid), dim3(512), 0, stream, g);      \
-    else                                                                                              \
-      hipLaunchKernelGGL((gru_step_mid_kernel<MB, BU, 4>), dim3(grid), dim3(256), 0, stream, g);      \
-  } while (0)
-      if ((kind & 8192) != 0) {       // 64 sequences per workgroup (only with 16 units, 8 waves)
-        hipLaunchKernelGGL((gru_step_mid_kernel<4, 16, 8>), dim3(grid), dim3(512), 0, stream, g);
-      } else if ((kind & 32) != 0) {
-        if (bu == 4) MID_LAUNCH_(1, 4);
-        else if (bu == 8) MID_LAUNCH_(1, 8);
-        else MID_LAUNCH_(1, 16);
-      } else {
-        if (bu == 4) MID_LAUNCH_(2, 4);
-        else if (bu == 8) MID_LAUNCH_(2, 8);
-        else MID_LAUNCH_(2, 16);
-      }
-#undef MID_LAUNCH_
-      break;
-    }
-    case 0:
-      if (vec) {
-        hipLaunchKernelGGL((gru_step_tiny_kernel<true, 4>), dim3(grid), dim3(kThreads), 0, stream, g);
-      } else {
-        hipLaunchKernelGGL((gru_step_tiny_kernel<false, 4>), dim3(grid), dim3(kThreads), 0, stream, g);
-      }
-      break;
-    case 2: {
-      // staging-bound loop: the 128-row tile halves the weight bytes per MFMA
-      const size_t smem = RingSmem<128, 3 * kGruBU>::kBytes;
-      hipLaunchKernelGGL((gru_step_kernel<true, 2, true>), dim3(grid), dim3(kThreads), smem, stream, g);
-      break;
-    }
-    default:
-      if (msub == 2) {
-        const size_t smem = TileSmem<128, 3 * kGruBU>::kBytes;
-        if (vec)
-          hipLaunchKernelGGL((gru_step_kernel<true, 2, false>), dim3(grid), dim3(kThreads), smem, stream, g);
-        else
-          hipLaunchKernelGGL((gru_step_kernel<false, 2, false>), dim3(grid), dim3(kThreads), smem, stream, g);
-      } else {
-        const size_t smem = TileSmem<64, 3 * kGruBU>::kBytes;
-        if (vec)
-          hipLaunchKernelGGL((gru_step_kernel<true, 1, false>), dim3(grid), dim3(kThreads), smem, stream, g);
-        else
-          hipLaunchKernelGGL((gru_step_kernel<false, 1, false>), dim3(grid), dim3(kThreads), smem, stream, g);
-      }
-  }
-}
-
-unsigned step_grid(const FwdJob& j, int kind, int S_t) {
-  const int H = j.b->H;
-  if ((kind & 3) == 3) {
-    const int bm = (kind & 8192) != 0 ? 64 : ((kind & 32) != 0 ? 16 : 32);
-    const int bu = (kind & 256) != 0 ? 4 : ((kind & 128) != 0 ? 8 : 16);
-    return static_cast<unsigned>((H + bu - 1) / bu) * ((S_t + bm - 1) / bm);
-  }
-  if ((kind & 3) == 0)
-    return static_cast<unsigned>((H + kTinyBU - 1) / kTinyBU) * ((S_t + kTinyBM - 1) / kTinyBM);
-  const int bm = ((kind & 3) == 2 || (kind & 2048) != 0) ? 128 : 64;
-  const int m_tiles = (S_t + bm - 1) / bm;
-  return static_cast<unsigned>(j.p.n_tiles) * m_tiles;
-}
-
-// Time steps of all jobs, step t of every still-running job in as few launches as kinds allow.
 int launch_attention(FwdJob& job, hipStream_t stream, int64_t row_end, bool pool);
 
-// Rows of the input projection in front of a chunked chain / per later chunk (launch_steps)
+// Rows of the input projection in front of a chunked chain / per later chunk (launch_hoisted_xproj)
 constexpr int64_t kXprojFirstRows = 512;
 static int64_t xproj_chunk_rows() { return tunables().xproj_chunk_rows.load(std::memory_order_relaxed); }
 static void launch_fwd_tail(FwdJob& j, hipStream_t stream) {
@@ -629,33 +601,89 @@ static void launch_fwd_tail(FwdJob& j, hipStream_t stream) {
 #undef FWD_TAIL_
 }
 
+// The launches of a job's hoisted input projection that run on a side stream, ahead of the steps
+// that read them: the early one-launch form, or the chunks behind the first (launch_hoisted_xproj)
 struct XprojPlan {
-  std::vector<int> step;        // first step of chunk c (c >= 1)
-  std::vector<hipEvent_t> ev;   // recorded behind chunk c's launch on the side stream
+  bool early = false;             // one launch on the side stream, queued before the first step ...
+  hipEvent_t early_ev = nullptr;  // ... and the event behind it (none: the host waited for it)
+  std::vector<int> step;          // first step of chunk c (c >= 1)
+  std::vector<hipEvent_t> ev;     // recorded behind chunk c's launch on the side stream
+};
+
+// An event recorded behind the work queued on `stream` so far.  When none can be recorded, the host
+// waits for that work instead (slower, never wrong) and the result is nullptr: nothing to wait for.
+static hipEvent_t record_or_sync(hipStream_t stream) {
+  hipEvent_t ev = event_get(false);
+  if (ev != nullptr && hipEventRecord(ev, stream) == hipSuccess) return ev;
+  event_put(ev, false);
+  (void)hipGetLastError();
+  (void)hipStreamSynchronize(stream);
+  return nullptr;
+}
+
+// Work of fp32 LDS-tiled steps, for the roofline of cmhse_timer_tiled
+struct TiledWork {
+  double flops = 0.0, bytes = 0.0;
+  // one step of S sequences: x_t in, h_{t-1} in, h_t out per sequence; the weights once per launch
+  void add(double S, double I, double H) {
+    flops += S * (2.0 * 3.0 * H * (I + H) + 14.0 * H);
+    bytes += S * 4.0 * (I + 2.0 * H) + 12.0 * H * (I + H);
+  }
+};
+
+// launch() between a timed event pair on `stream`, with `work` added to the timer; without a timer
+// or a pair of events, just the launch.
+template <class Launch>
+static void timed_launch(Timer* timer, hipStream_t stream, const TiledWork& work, Launch launch) {
+  hipEvent_t e0 = timer != nullptr ? event_get(true) : nullptr;
+  hipEvent_t e1 = e0 != nullptr ? event_get(true) : nullptr;
+  if (e1 == nullptr) {   // no pair: release the first, time nothing
+    event_put(e0, true);
+    launch();
+    return;
+  }
+  (void)hipEventRecord(e0, stream);
+  launch();
+  (void)hipEventRecord(e1, stream);
+  timer->tiled_events.push_back(e0);
+  timer->tiled_events.push_back(e1);
+  timer->tiled_flops += work.flops;
+  timer->tiled_bytes += work.bytes;
+}
+
+// The streams of one launch_steps call: the caller's, the call's side stream (optional) and the one
+// each request's steps go to now.
+struct StepStreams {
+  hipStream_t main, side;
+  hipStream_t js[kMaxJobs];
+  bool forked;                  // a request has moved to the side stream
+  // request k moves to the side stream (at most once, ordered behind what the caller's stream holds)
+  void fork(int k) {
+    if (side == nullptr || js[k] != main) return;
+    stream_after(side, main);
+    js[k] = side;
+    forked = true;
+  }
 };
 
 // The requests of a call that run an fp32 LDS-tiled step at time step t and will go on doing so
 // TOGETHER: which of them (in_chain), up to which step (end, exclusive; 0 = no chain here), with
-// which tile height (kind, bit 2048 = 128 rows) and on which stream.
+// which tile (shape: rows and vec) and on which stream.
 struct ChainPlan {
   bool in_chain[kMaxJobs];
-  int end, kind;
+  int end;
+  StepShape shape;
   hipStream_t stream;
 };
 
-static ChainPlan plan_chain(const FwdJob* jobs, int n, int t, const int* kind, const bool* done,
+static ChainPlan plan_chain(const FwdJob* jobs, int n, int t, const StepShape* shape, const bool* done,
                             const hipStream_t* js, int tiled_wgs) {
-  ChainPlan c;
-  for (int k = 0; k < kMaxJobs; ++k) c.in_chain[k] = false;
-  c.end = 0;
-  c.kind = -1;
-  c.stream = nullptr;
-
+  ChainPlan c{};
   const int min_steps = multi_step_knob(tunables().chain_min_steps);
   int n_c = 0, tiles_c = -1;
   bool ok = min_steps > 0;
   for (int k = 0; k < n && ok; ++k) {
-    if (done[k] || (kind[k] & 3) != 1) continue;
+    if (done[k] || shape[k].family != StepShape::Tiled) continue;
     const FwdJob& j = jobs[k];
     // (H % 32: a state row must be whole 128-byte cache lines — a reader that pulled a line
     // shared with the NEXT row tile's first row into its L2 before that row was written would
@@ -663,10 +691,10 @@ static ChainPlan plan_chain(const FwdJob* jobs, int n, int t, const int* kind, c
     if (t < j.chain_until || j.save || j.bf3 || j.tail_lo >= 0 || j.b->H % 32 != 0) {
       ok = false;
     } else if (n_c == 0) {
-      c.kind = kind[k];
+      c.shape = shape[k];
       tiles_c = j.p.n_tiles;
       c.stream = js[k];
-    } else if (kind[k] != c.kind || j.p.n_tiles != tiles_c || js[k] != c.stream) {
+    } else if (shape[k] != c.shape || j.p.n_tiles != tiles_c || js[k] != c.stream) {
       ok = false;
     }
     c.in_chain[k] = true;
@@ -686,7 +714,7 @@ static ChainPlan plan_chain(const FwdJob* jobs, int n, int t, const int* kind, c
         tall *= 4;
         break;
       }
-    c.kind = (c.kind & ~2048) | ((tall > 0 && tiled_wgs >= tall) ? 2048 : 0);
+    c.shape.rows = (tall > 0 && tiled_wgs >= tall) ? 128 : 64;
     c.end = t + 1;
     while (c.end - t < kChainMaxSteps) {
       bool same = true;
@@ -706,13 +734,11 @@ static ChainPlan plan_chain(const FwdJob* jobs, int n, int t, const int* kind, c
     // one workgroup per task: HIP rejects a launch of more than 2^32 - 1 threads, i.e. 2^24 - 1
     // workgroups of 256 (halve the chain until it fits)
     for (;;) {
-      const int bm_c = (c.kind & 2048) != 0 ? 128 : 64;
       uint64_t units_c = 0;
       for (int q = t; q < c.end; ++q)
         for (int k = 0; k < n; ++k)
-          if (c.in_chain[k])
-            units_c += static_cast<uint64_t>((jobs[k].b->step_count_host[q] + bm_c - 1) / bm_c);
-      if (units_c * static_cast<uint64_t>(tiles_c) * kThreads <= 0xffffffffULL || c.end - t <= 1) break;
+          if (c.in_chain[k]) units_c += static_cast<uint64_t>(c.shape.row_tiles(jobs[k].b->step_count_host[q]));
+      if (units_c * static_cast<uint64_t>(tiles_c) * (64 * c.shape.waves) <= 0xffffffffULL || c.end - t <= 1) break;
       c.end = t + (c.end - t) / 2;
     }
     ok = c.end - t >= min_steps;
@@ -733,7 +759,6 @@ static void launch_chain(FwdJob* jobs, int n, int t, const ChainPlan& c, Timer* 
   cg.nsteps = c.end - t;
   cg.ticket = nullptr;
   unsigned* abort_word = nullptr;
-  const int bm = (c.kind & 2048) != 0 ? 128 : 64;
   for (int k = 0; k < n; ++k) {
     if (!c.in_chain[k]) continue;
     FwdJob& j = jobs[k];
@@ -741,7 +766,7 @@ static void launch_chain(FwdJob* jobs, int n, int t, const ChainPlan& c, Timer* 
     cg.j[q] = j.p;
     cg.n_tiles = j.p.n_tiles;
     cg.step_off[q] = j.b->step_off;
-    cg.rt_stride[q] = (j.b->step_count_host[t] + bm - 1) / bm;
+    cg.rt_stride[q] = c.shape.row_tiles(j.b->step_count_host[t]);
     unsigned* words = reinterpret_cast<unsigned*>(j.wsb + j.L.chain_sync);
     cg.done[q] = words + 64;
     (void)hipMemsetAsync(words, 0, 256 + sizeof(unsigned) * static_cast<size_t>(cg.nsteps) * cg.rt_stride[q],
@@ -763,16 +788,13 @@ static void launch_chain(FwdJob* jobs, int n, int t, const ChainPlan& c, Timer* 
   const int n_phases = cg.nsteps;
   uint32_t count[kChainPhases];
   for (int p = 0; p < kChainPhases; ++p) count[p] = 0;
-  double flops = 0.0, bytes = 0.0;
+  TiledWork work;
   for (int sidx = 0; sidx < cg.nsteps; ++sidx) {
     for (int k = 0; k < n; ++k) {
       if (!c.in_chain[k]) continue;
       const int S_k = jobs[k].b->step_count_host[t + sidx];
-      const unsigned rt = static_cast<unsigned>((S_k + bm - 1) / bm);
-      count[sidx] += rt * cols;
-      const double I = jobs[k].p.I, H = jobs[k].p.H;
-      flops += S_k * (2.0 * 3.0 * H * (I + H) + 14.0 * H);
-      bytes += S_k * 4.0 * (I + 2.0 * H) + 12.0 * H * (I + H);
+      count[sidx] += static_cast<unsigned>(c.shape.row_tiles(S_k)) * cols;
+      work.add(S_k, jobs[k].p.I, jobs[k].p.H);
     }
   }
   uint64_t total = 0;
@@ -782,34 +804,10 @@ static void launch_chain(FwdJob* jobs, int n, int t, const ChainPlan& c, Timer* 
   }
   cg.sync = make_grid_sync(nullptr, abort_word);
   const unsigned cgrid = static_cast<unsigned>(total * static_cast<uint64_t>(nq));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timer != nullptr) {
-    e0 = event_get(true);
-    e1 = e0 ? event_get(true) : nullptr;
-    if (e0 && !e1) {
-      event_put(e0, true);
-      e0 = nullptr;
-    }
-    if (e0 && e1) (void)hipEventRecord(e0, c.stream);
-  }
-  const bool cvec = (c.kind & 4) == 0;
-#define CHAIN_LAUNCH_(V, M, SMEM) \
-  hipLaunchKernelGGL((gru_step_chain_kernel<V, M>), dim3(cgrid), dim3(kThreads), SMEM, c.stream, cg)
-  if (bm == 128) {
-    if (cvec) CHAIN_LAUNCH_(true, 2, (TileSmem<128, 3 * kGruBU>::kBytes));
-    else CHAIN_LAUNCH_(false, 2, (TileSmem<128, 3 * kGruBU>::kBytes));
-  } else {
-    if (cvec) CHAIN_LAUNCH_(true, 1, (TileSmem<64, 3 * kGruBU>::kBytes));
-    else CHAIN_LAUNCH_(false, 1, (TileSmem<64, 3 * kGruBU>::kBytes));
-  }
-#undef CHAIN_LAUNCH_
-  if (e0 && e1) {
-    (void)hipEventRecord(e1, c.stream);
-    timer->tiled_events.push_back(e0);
-    timer->tiled_events.push_back(e1);
-    timer->tiled_flops += flops;
-    timer->tiled_bytes += bytes;
-  }
+  const StepKernel sk = step_kernel(c.shape);
+  timed_launch(timer, c.stream, work, [&] {
+    hipLaunchKernelGGL(sk.chain, dim3(cgrid), dim3(64 * c.shape.waves), sk.smem, c.stream, cg);
+  });
 }
 
 // `out` of job j is final behind everything queued on `stream` so far: tell the caller's event.
@@ -819,6 +817,108 @@ static inline void mark_ready(FwdJob& j, hipStream_t stream) {
   j.ready_marked = true;
 }
 
+// Step t_mid of job j, on `stream`: the hoisted input projection of its steps >= t_mid — waited for
+// when it was launched early (xp), read from the token projection table, or launched now.
+static void launch_hoisted_xproj(FwdJob& j, hipStream_t stream, XprojPlan& xp) {
+  const cmhse_seq_batch* b = j.b;
+  const int t = j.t_mid;
+  // A chain that is small-batch from its first step (a training batch) with a side stream:
+  // only the projection of the first steps stands in front of the chain; the rest is cut
+  // into chunks of time steps that run on the side stream BESIDE the chain, step t waiting
+  // (event) for the chunk that holds its rows.  A GEMM of img_dim = 2048 rows is as long as
+  // the whole 80-step chain it used to precede.
+  const bool chunked = j.side_stream != nullptr && j.side_stream != stream && t == 0 && !j.p.gx_per_seq &&
+                       xproj_chunk_rows() > 0 && j.sum_T >= 4 * xproj_chunk_rows();
+  // the hoisted projection reads the inputs of the steps it covers: wait for their uploads
+  // (cmhse_pull_steps chunks still in flight) — all remaining steps for the one-launch form,
+  // chunk by chunk for the chunked one (a host-fed training step: the chain starts as soon as
+  // the first steps' rows have crossed PCIe, the rest arrives under it)
+  auto wait_uploads = [&](hipStream_t st, int q0, int q1) {
+    if (b->step_events_host == nullptr) return;
+    for (int q = q0; q < q1; ++q)
+      if (b->step_events_host[q] != nullptr)
+        (void)hipStreamWaitEvent(st, static_cast<hipEvent_t>(const_cast<void*>(b->step_events_host[q])), 0);
+  };
+  if (xp.early) {
+    if (xp.early_ev != nullptr) (void)hipStreamWaitEvent(stream, xp.early_ev, 0);
+    event_put(xp.early_ev, false);
+    xp.early = false;
+    xp.early_ev = nullptr;
+    return;
+  }
+  if (j.p.tok_tab != nullptr) return;   // the small-batch steps read their gx rows from the table (queued in front)
+  if (!chunked) {
+    wait_uploads(stream, t + 1, b->Tmax);
+    launch_xproj(j, stream);
+    return;
+  }
+  int64_t row = 0, chunk_begin = 0;
+  int t0 = 0;
+  for (int q = 0; q < b->Tmax; ++q) {
+    row += b->step_count_host[q];
+    const int64_t want = (t0 == 0) ? kXprojFirstRows : xproj_chunk_rows();
+    if (row - chunk_begin >= want || q == b->Tmax - 1) {
+      if (t0 == 0) {
+        wait_uploads(stream, 1, q + 1);
+        launch_xproj(j, stream, 0, row);
+        stream_after(j.side_stream, stream);     // fork: the inputs are ready
+      } else {
+        wait_uploads(j.side_stream, t0, q + 1);
+        launch_xproj(j, j.side_stream, chunk_begin, row);
+        if (hipEvent_t ev = record_or_sync(j.side_stream)) {
+          xp.step.push_back(t0);
+          xp.ev.push_back(ev);
+        }
+      }
+      chunk_begin = row;
+      t0 = q + 1;
+    }
+  }
+}
+
+// (b) A request whose chain ends at step t while others go on: the others continue on the side
+// stream and its attention pass starts now on the caller's stream, so the two overlap (the
+// tail is a few sequences per step: latency-bound launches on an otherwise idle chip).
+static void launch_early_attention(FwdJob* jobs, int n, int t, int Tmax, StepStreams& ss) {
+  const hipStream_t* js = ss.js;
+  for (int k = 0; k < n; ++k) {   // a chain on its own stream pools as soon as it ends
+    FwdJob& j = jobs[k];
+    if (!j.pooled && js[k] != ss.main && js[k] == j.own_stream && j.pool_mode == CMHSE_POOL_ATTN &&
+        t == j.b->Tmax - 1 && launch_attention(j, js[k], j.sum_T, true) == CMHSE_OK) {
+      j.pooled = true;
+      mark_ready(j, js[k]);
+    }
+  }
+  for (int k = 0; k < n; ++k) {
+    FwdJob& j = jobs[k];
+    if (j.pooled || ss.side == nullptr || js[k] != ss.main || j.pool_mode != CMHSE_POOL_ATTN ||
+        t != j.b->Tmax - 1 || t == Tmax - 1)
+      continue;
+    bool others = false;
+    for (int m = 0; m < n; ++m)
+      if (m != k && t < jobs[m].b->Tmax - 1) {
+        ss.fork(m);
+        others = true;
+      }
+    if (!others) continue;
+    if (launch_attention(j, ss.main, j.sum_T, true) == CMHSE_OK) {
+      j.pooled = true;
+      mark_ready(j, ss.main);      // this request's rows can leave while the others' tail runs
+    }
+    // ... and behind it the attention projection of what the OTHER attention-pooled chains have
+    // produced so far: only the rows of their remaining tail steps are left for after the tail
+    for (int m = 0; m < n; ++m) {
+      FwdJob& o = jobs[m];
+      if (m == k || o.pool_mode != CMHSE_POOL_ATTN || o.pooled || t >= o.b->Tmax - 1 || o.off <= 0 ||
+          o.own_stream != nullptr)
+        continue;
+      if (js[m] != ss.main) stream_after(ss.main, js[m]);   // its steps <= t
+      (void)launch_attention(o, ss.main, o.off, false);
+    }
+  }
+}
+
+// Time steps of all jobs: step t of every still-running job in as few launches as shapes allow.
 int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
   int Tmax = 0, launches = 0;
   XprojPlan plan[kMaxJobs];
@@ -829,10 +929,11 @@ int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
   //       workgroup slots) — its short launches, and later its long few-sequence tail, then hide
   //       under the other chain's steps instead of following each of them;
   //   (b) another chain has ended and starts its attention pass on the caller's stream.
-  hipStream_t side = nullptr;
+  StepStreams ss{main_stream, nullptr, {}, false};
   for (int k = 0; k < n; ++k)
-    if (jobs[k].tail_stream != nullptr && jobs[k].tail_stream != main_stream) side = jobs[k].tail_stream;
-  hipStream_t js[kMaxJobs];
+    if (jobs[k].tail_stream != nullptr && jobs[k].tail_stream != main_stream) ss.side = jobs[k].tail_stream;
+  const hipStream_t side = ss.side;
+  hipStream_t* const js = ss.js;
   for (int k = 0; k < kMaxJobs; ++k) js[k] = main_stream;
   // A request with a stream of its own (the towers of a training step: independent latency chains
   // that should advance side by side from their first step) runs there from start to end; the
@@ -891,8 +992,6 @@ int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
   // stood in front of the text tower's few-sequence tail — the end of a rank's share of the split is
   // that tail, 1.7 of its 41 ms were this GEMM (profiles/r05_rank_share.txt).  Step t_mid waits for
   // the event.  (Inputs still crossing PCIe — step_events_host — keep the in-order form.)
-  hipEvent_t early_xproj[kMaxJobs];
-  for (int k = 0; k < kMaxJobs; ++k) early_xproj[k] = nullptr;
   if (side != nullptr && tunables().early_xproj.load(std::memory_order_relaxed) != 0) {
     bool side_ready = false;
     for (int k = 0; k < n; ++k) {
@@ -905,61 +1004,47 @@ int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
         side_ready = true;
       }
       launch_xproj(j, side);
-      hipEvent_t ev = event_get(false);
-      if (ev != nullptr && hipEventRecord(ev, side) == hipSuccess) {
-        early_xproj[k] = ev;
-      } else {                               // no event: order the whole stream instead
-        event_put(ev, false);
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(side);
-        early_xproj[k] = reinterpret_cast<hipEvent_t>(static_cast<uintptr_t>(1));   // done, nothing to wait for
-      }
+      plan[k].early = true;
+      plan[k].early_ev = record_or_sync(side);
     }
   }
-  bool forked = false;
-  auto fork = [&](int k) {
-    if (side == nullptr || js[k] != main_stream) return;
-    stream_after(side, main_stream);
-    js[k] = side;
-    forked = true;
-  };
+  const StepShape tile64{StepShape::Tiled, true, 64, kGruBU, 4};   // the workgroups tiled_wgs counts
   for (int k = 0; k < n; ++k) Tmax = jobs[k].b->Tmax > Tmax ? jobs[k].b->Tmax : Tmax;
   for (int t = 0; t < Tmax; ++t) {
-    int kind[kMaxJobs];
+    StepShape shape[kMaxJobs];
     bool done[kMaxJobs];
     bool any_tiled = false;
     int mid_blocks = 0;
     for (int k = 0; k < n; ++k)
       if (t < jobs[k].b->Tmax && t >= jobs[k].t_mid && !(jobs[k].tail_lo >= 0 && t >= jobs[k].tail_lo))
         mid_blocks += mid_m_blocks(jobs[k].b->step_count_host[t]);
-    bool alone = !forked;
+    bool alone = !ss.forked;
     int tiled_wgs = 0;
     for (int k = 0; k < n; ++k)
       if (t < jobs[k].b->Tmax && t < jobs[k].t_mid) {
         alone = false;   // a tiled / tiny step runs too
-        const int S_k = jobs[k].b->step_count_host[t];
         if (jobs[k].kind_count[t] > tiny_max_seqs() && !jobs[k].bf3)
-          tiled_wgs += jobs[k].p.n_tiles * ((S_k + 63) / 64);
+          tiled_wgs += static_cast<int>(tile64.grid(jobs[k].b->H, jobs[k].b->step_count_host[t]));
       }
     for (int k = 0; k < n; ++k) {
       done[k] = t >= jobs[k].b->Tmax;
       if (done[k]) continue;
       FwdJob& j = jobs[k];
       j.p.t = t;
-      kind[k] = step_kind(j, j.b->step_count_host[t], mid_blocks, alone, tiled_wgs);
-      any_tiled = any_tiled || (kind[k] & 3) == 1 || (kind[k] & 3) == 2;
+      shape[k] = step_shape(j, j.b->step_count_host[t], mid_blocks, alone, tiled_wgs);
+      any_tiled = any_tiled || shape[k].tiled();
     }
     // Step chain (gru_step_chain_kernel): when the requests that run an fp32 LDS-tiled step now go
     // on doing so together for at least chain_min_steps steps, those steps are ONE launch, queued
     // below; the requests are skipped by the per-step launches until the chain's last step.
-    const ChainPlan chain = plan_chain(jobs, n, t, kind, done, js, tiled_wgs);
+    const ChainPlan chain = plan_chain(jobs, n, t, shape, done, js, tiled_wgs);
     for (int k = 0; k < n; ++k) {
       if (done[k]) continue;
       FwdJob& j = jobs[k];
       const int S_t = j.b->step_count_host[t];
       if (j.tail_lo >= 0 && t >= j.tail_lo) {      // the resident kernel does this step
         if (t == j.tail_lo) {
-          if (any_tiled) fork(k);                  // (a), as for a small-batch step below
+          if (any_tiled) ss.fork(k);               // (a), as for a small-batch step below
           for (size_t c = 0; c < plan[k].step.size(); ++c)
             if (plan[k].ev[c] != nullptr) {        // its rows' projection chunks, all of them
               (void)hipStreamWaitEvent(js[k], plan[k].ev[c], 0);
@@ -973,71 +1058,11 @@ int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
         done[k] = true;
         continue;
       }
-      const bool small = (kind[k] & 3) == 0 || (kind[k] & 3) == 3;
-      if (small && any_tiled) fork(k);                                       // (a)
+      if (!shape[k].tiled() && any_tiled) ss.fork(k);                        // (a)
       hipStream_t stream = js[k];
       if (j.b->step_events_host != nullptr && j.b->step_events_host[t] != nullptr)
         (void)hipStreamWaitEvent(stream, static_cast<hipEvent_t>(const_cast<void*>(j.b->step_events_host[t])), 0);
-      if (t == j.t_mid) {
-        // A chain that is small-batch from its first step (a training batch) with a side stream:
-        // only the projection of the first steps stands in front of the chain; the rest is cut
-        // into chunks of time steps that run on the side stream BESIDE the chain, step t waiting
-        // (event) for the chunk that holds its rows.  A GEMM of img_dim = 2048 rows is as long as
-        // the whole 80-step chain it used to precede.
-        const bool chunked = j.side_stream != nullptr && j.side_stream != stream && t == 0 &&
-                             j.t_mid == 0 && !j.p.gx_per_seq && xproj_chunk_rows() > 0 && j.sum_T >= 4 * xproj_chunk_rows();
-        // the hoisted projection reads the inputs of the steps it covers: wait for their uploads
-        // (cmhse_pull_steps chunks still in flight) — all remaining steps for the one-launch form,
-        // chunk by chunk for the chunked one (a host-fed training step: the chain starts as soon as
-        // the first steps' rows have crossed PCIe, the rest arrives under it)
-        auto wait_uploads = [&](hipStream_t st, int q0, int q1) {
-          if (j.b->step_events_host == nullptr) return;
-          for (int q = q0; q < q1; ++q)
-            if (j.b->step_events_host[q] != nullptr)
-              (void)hipStreamWaitEvent(st, static_cast<hipEvent_t>(const_cast<void*>(j.b->step_events_host[q])), 0);
-        };
-        if (early_xproj[k] != nullptr) {          // launched on the side stream before the first step
-          if (early_xproj[k] != reinterpret_cast<hipEvent_t>(static_cast<uintptr_t>(1))) {
-            (void)hipStreamWaitEvent(stream, early_xproj[k], 0);
-            event_put(early_xproj[k], false);
-          }
-          early_xproj[k] = nullptr;
-        } else if (j.p.tok_tab != nullptr) {
-          // the small-batch steps read their gx rows from the token projection table (queued above)
-        } else if (!chunked) {
-          wait_uploads(stream, t + 1, j.b->Tmax);
-          launch_xproj(j, stream);
-        } else {
-          XprojPlan& xp = plan[k];
-          int64_t row = 0, chunk_begin = 0;
-          int t0 = 0;
-          for (int q = 0; q < j.b->Tmax; ++q) {
-            row += j.b->step_count_host[q];
-            const int64_t want = (t0 == 0) ? kXprojFirstRows : xproj_chunk_rows();
-            if (row - chunk_begin >= want || q == j.b->Tmax - 1) {
-              if (t0 == 0) {
-                wait_uploads(stream, 1, q + 1);
-                launch_xproj(j, stream, 0, row);
-                stream_after(j.side_stream, stream);     // fork: the inputs are ready
-              } else {
-                wait_uploads(j.side_stream, t0, q + 1);
-                launch_xproj(j, j.side_stream, chunk_begin, row);
-                hipEvent_t ev = event_get(false);
-                if (ev != nullptr && hipEventRecord(ev, j.side_stream) == hipSuccess) {
-                  xp.step.push_back(t0);
-                  xp.ev.push_back(ev);
-                } else {                                  // no event: order the whole stream instead
-                  event_put(ev, false);
-                  (void)hipGetLastError();
-                  (void)hipStreamSynchronize(j.side_stream);
-                }
-              }
-              chunk_begin = row;
-              t0 = q + 1;
-            }
-          }
-        }
-      }
+      if (t == j.t_mid) launch_hoisted_xproj(j, stream, plan[k]);
       for (size_t c = 0; c < plan[k].step.size(); ++c)
         if (plan[k].step[c] == t) {     // the chunk that holds step t's rows
           (void)hipStreamWaitEvent(stream, plan[k].ev[c], 0);
@@ -1062,90 +1087,32 @@ int launch_steps(FwdJob* jobs, int n, hipStream_t main_stream, Timer* timer) {
       GruStepGroup g;
       g.n = 0;
       unsigned grid = 0;
+      TiledWork work;
       hipStream_t stream = js[k];
       for (int m = k; m < n; ++m) {   // same kernel, same stream: one launch
-        if (done[m] || kind[m] != kind[k] || js[m] != stream) continue;
+        if (done[m] || shape[m] != shape[k] || js[m] != stream) continue;
         g.j[g.n] = jobs[m].p;
         g.start[g.n] = grid;
-        grid += step_grid(jobs[m], kind[m], jobs[m].p.S_t);
+        grid += shape[m].grid(jobs[m].b->H, jobs[m].p.S_t);
+        work.add(jobs[m].p.S_t, jobs[m].p.I, jobs[m].p.H);
         ++g.n;
         done[m] = true;
       }
       for (int m = g.n; m < kMaxJobs; ++m) g.start[m] = 0xffffffffu;
-      const bool stamp = timer != nullptr && ((kind[k] & 3) == 1 || (kind[k] & 3) == 2);
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (stamp) {
-        e0 = event_get(true);
-        e1 = e0 ? event_get(true) : nullptr;
-        if (e0 && !e1) {   // no pair: release the first, time nothing
-          event_put(e0, true);
-          e0 = nullptr;
-        }
-        if (e0 && e1) (void)hipEventRecord(e0, stream);
-      }
-      launch_group(g, kind[k], grid, stream);
-      if (stamp && e0 && e1) {
-        (void)hipEventRecord(e1, stream);
-        timer->tiled_events.push_back(e0);
-        timer->tiled_events.push_back(e1);
-        for (int q = 0; q < g.n; ++q) {
-          const double I = g.j[q].I, H = g.j[q].H;
-          timer->tiled_flops += g.j[q].S_t * (2.0 * 3.0 * H * (I + H) + 14.0 * H);
-          // x_t in, h_{t-1} in, h_t out per sequence; the weights once per launch
-          timer->tiled_bytes += g.j[q].S_t * 4.0 * (I + 2.0 * H) + 12.0 * H * (I + H);
-        }
-      }
+      timed_launch(shape[k].tiled() ? timer : nullptr, stream, work, [&] { launch_group(g, shape[k], grid, stream); });
       ++launches;
     }
-    // (b) A request whose chain ends here while others go on: the others continue on the side
-    // stream and its attention pass starts now on the caller's stream, so the two overlap (the
-    // tail is a few sequences per step: latency-bound launches on an otherwise idle chip).
-    for (int k = 0; k < n; ++k) {   // a chain on its own stream pools as soon as it ends
-      FwdJob& j = jobs[k];
-      if (!j.pooled && js[k] != main_stream && js[k] == j.own_stream && j.pool_mode == CMHSE_POOL_ATTN &&
-          t == j.b->Tmax - 1 && launch_attention(j, js[k], j.sum_T, true) == CMHSE_OK) {
-        j.pooled = true;
-        mark_ready(j, js[k]);
-      }
-    }
-    for (int k = 0; k < n; ++k) {
-      FwdJob& j = jobs[k];
-      if (j.pooled || side == nullptr || js[k] != main_stream || j.pool_mode != CMHSE_POOL_ATTN ||
-          t != j.b->Tmax - 1 || t == Tmax - 1)
-        continue;
-      bool others = false;
-      for (int m = 0; m < n; ++m)
-        if (m != k && t < jobs[m].b->Tmax - 1) {
-          fork(m);
-          others = true;
-        }
-      if (!others) continue;
-      if (launch_attention(j, main_stream, j.sum_T, true) == CMHSE_OK) {
-        j.pooled = true;
-        mark_ready(j, main_stream);      // this request's rows can leave while the others' tail runs
-      }
-      // ... and behind it the attention projection of what the OTHER attention-pooled chains have
-      // produced so far: only the rows of their remaining tail steps are left for after the tail
-      for (int m = 0; m < n; ++m) {
-        FwdJob& o = jobs[m];
-        if (m == k || o.pool_mode != CMHSE_POOL_ATTN || o.pooled || t >= o.b->Tmax - 1 || o.off <= 0 ||
-            o.own_stream != nullptr)
-          continue;
-        if (js[m] != main_stream) stream_after(main_stream, js[m]);   // its steps <= t
-        (void)launch_attention(o, main_stream, o.off, false);
-      }
-    }
+    launch_early_attention(jobs, n, t, Tmax, ss);
   }
   // an early projection nobody waited for (defensive: step t_mid always does) still owns an event, and
   // the side stream then holds work the caller's stream has not been ordered behind
   bool side_pending = false;
   for (int k = 0; k < kMaxJobs; ++k) {
-    if (early_xproj[k] == nullptr) continue;
-    if (early_xproj[k] != reinterpret_cast<hipEvent_t>(static_cast<uintptr_t>(1))) event_put(early_xproj[k], false);
-    early_xproj[k] = nullptr;
+    if (!plan[k].early) continue;
+    event_put(plan[k].early_ev, false);
     side_pending = true;
   }
-  if (forked || side_pending) stream_after(main_stream, side);   // rejoin: what follows is ordered on the caller's stream
+  if (ss.forked || side_pending) stream_after(main_stream, side);   // rejoin: what follows is ordered on the caller's stream
   return launches;
 }
 
