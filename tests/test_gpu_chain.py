@@ -13,6 +13,8 @@ from gpu_common import *  # noqa: F401,F403,E402
 from gpu_common import (_blas_threads, _check_train_step_vs_oracle, _full_opt, _nccl_worker, _np_batches,  # noqa: F401,E402
                         _np_state_dicts, _plan_setup, _RecordForward, _robust_rank_rows)
 
+import bptt_shapes  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
@@ -228,9 +230,7 @@ def test_forward_tail_as_one_resident_kernel(dev, oracle, pool, cls, H, S, n_lon
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('pool,cls,H,S,n_long', [('attention', 'Attention', 32, 11, 13), ('maxout', 'Maxout', 48, 40, 13),
-                                                 ('seq2seq', 'Seq2Seq', 128, 23, 13), ('attention', 'Attention', 1024, 32, 13),
-                                                 ('maxout', 'Maxout', 64, 40, 29), ('attention', 'Attention', 1024, 32, 30)])
+@pytest.mark.parametrize('pool,cls,H,S,n_long', bptt_shapes.TAIL_CASES)
 def test_bptt_tail_as_one_resident_kernel(dev, oracle, pool, cls, H, S, n_long, tune):
   """The few-sequence tail of a BPTT chain — the steps with at most 16 active sequences at the end
   of whole-paragraph / whole-video sequences (up to 32: one or two 16-row blocks per workgroup) — inside ONE resident kernel (gru_bwd_tail_kernel:
@@ -238,11 +238,12 @@ def test_bptt_tail_as_one_resident_kernel(dev, oracle, pool, cls, H, S, n_long, 
   non-coherent L2s) against one launch per step (bwd_tail_min_steps = 0): every gradient equal to
   fp32 rounding and bitwise reproducible run after run, for H = 32 ... 1024 (2 ... 24 16-k blocks per wave, ragged ownership at the
   small ones), a chain that is ALL tail (S = 11), one whose tail starts mid-way, and against the
-  float64 oracle."""
+  float64 oracle.  The cases run every KB instantiation with one and with two 16-row blocks
+  (tests/test_bptt_shapes_cpu.py)."""
   from cmhse_amd import layers
   rng = np.random.RandomState(5 + H)
   I = 20 if H < 1024 else 64
-  T = 37
+  T = bptt_shapes.TAIL_T
   torch.manual_seed(9)
   layer = getattr(layers, cls)(I, H)
   with torch.no_grad():
@@ -250,10 +251,7 @@ def test_bptt_tail_as_one_resident_kernel(dev, oracle, pool, cls, H, S, n_long, 
     layer.rnn.bias_hh_l0.normal_(0, 0.1)
   sd = {'rnn.' + k: v.detach().numpy().astype(np.float64) for k, v in layer.state_dict().items()}
   layer = layer.to(dev)
-  lens = rng.randint(1, 9, size=S)                 # most sequences end early ...
-  long_ones = rng.permutation(S)[:min(S, n_long)]   # n_long > 16: a tail of two 16-row blocks
-  lens[long_ones] = rng.randint(10, T + 1, size=len(long_ones))   # ... at most 13 run on
-  lens[long_ones[0]] = T
+  lens = bptt_shapes.tail_case_lens(rng, S, n_long, T)   # most sequences end early, n_long run on
   assert (lens > 9).sum() <= 32 and lens.max() == T
   x = np.zeros((S, T, I), dtype=np.float32)
   for i, l in enumerate(lens):
@@ -276,13 +274,14 @@ def test_bptt_tail_as_one_resident_kernel(dev, oracle, pool, cls, H, S, n_long, 
     # the gate arithmetic of the two kernels into different FMAs: equal to fp32 rounding
     assert float((a - b).abs().max()) <= 4e-6 * max(1e-6, float(a.abs().max()))
     assert torch.equal(b, c), 'not reproducible from run to run'
-  if H <= 128:
+  with _blas_threads():
     _, cache = oracle.pooled_gru_forward_cache(pool, x, lens, sd, h0)
     grads, dx, dh0 = oracle.pooled_gru_backward(cache, w.astype(np.float64))
-    grad_close(resident[0].cpu().numpy()[:, :dx.shape[1]], dx, pool + ' dx')
-    grad_close(resident[1].cpu().numpy(), dh0, pool + ' dh0')
-    for (pn, _), got in zip(layer.named_parameters(), resident[2:]):
-      grad_close(got.cpu().numpy(), grads['rnn.' + pn], pool + ' ' + pn)
+  tag = '%s H%d S%d' % (pool, H, S)
+  grad_close(resident[0].cpu().numpy()[:, :dx.shape[1]], dx, tag + ' dx')
+  grad_close(resident[1].cpu().numpy(), dh0, tag + ' dh0')
+  for (pn, _), got in zip(layer.named_parameters(), resident[2:]):
+    grad_close(got.cpu().numpy(), grads['rnn.' + pn], tag + ' ' + pn)
 
 
 @pytest.mark.parametrize('shape', ['one_xcd_queue', 'two_requests', 'full_width', 'scalar_loads', 'long_chain',

@@ -4,7 +4,7 @@
   python tools/mutation_check.py build [name ...]   (build container: hipcc, no GPU needed)
       copies cmhse_amd/csrc to build/mutants/<name>/, applies ONE source edit per mutant, and builds
       build/mutants/libcmhse_<name>.so (same ABI; the product sources and library are untouched).
-  python tools/mutation_check.py run          (GPU box)
+  python tools/mutation_check.py run [name ...]     (GPU box)
       runs the selected GPU tests once per mutant with CMHSE_HIP_LIB pointing at it and reports
       which tests FAILED — a mutant that no test kills is a hole in the suite.  Also runs the same
       selection on the product library (must pass).
@@ -13,6 +13,9 @@ Mutants:
   attn_eps_fwd   gru_attention.hpp: the masked softmax's `+ 0.0001f` (layers.py:158-162) -> `+ 0.0f`
   attn_eps_bwd   bwd_pool_kernels.hpp: the same epsilon in the attention backward
   norm_by_n, gru_bhn_outside_r(_tiled), rank_counts_ties, l2norm_eps   (round 6, second batch) see MUTANTS
+  bwd_step_combine_4_waves, bwd_step_drops_carry, bwd_gates_dz, bwd_tail_four_blocks   the BPTT step
+                 shapes (killed by tests/test_gpu_bptt_shapes.py; the tail one by test_gpu_chain.py's
+                 resident-tail test)
 """
 import os
 import shutil
@@ -44,11 +47,25 @@ MUTANTS = {
     'max_violation_sums': ('sim.hip', 'total += p.max_violation ? static_cast<double>(mx) : sum;', 'total += sum;'),
     # F.normalize's eps (model.py l2norm of the encoder outputs): a zero row stays zero, x / max(|x|, 1e-12)
     'l2norm_eps': ('gru_rows.hpp', 's_inv = 1.0f / fmaxf(sqrtf(t), 1e-12f);', 's_inv = 1.0f / sqrtf(t);'),
+    # BPTT step shapes (tests/test_gpu_bptt_shapes.py): value-only edits, no address, grid or barrier moves.
+    # The 32 x 32 step tile's LDS combine adds the partials of 4 waves only: wrong for the 8-wave kernels
+    'bwd_step_combine_4_waves': ('bwd_step_kernels.hpp', 'for (int w = 0; w < NW; ++w) part += red[w][reg][lb + j];',
+                                 'for (int w = 0; w < 4; ++w) part += red[w][reg][lb + j];'),
+    # ... its epilogue drops the carried dh_{t+1} z_{t+1} (every gru_bwd_step_kernel instantiation)
+    'bwd_step_drops_carry': ('bwd_step_kernels.hpp', '      rec += part;', '      rec = part;'),
+    # the split step's gate kernel: dz without the sigmoid's (1 - z) factor
+    'bwd_gates_dz': ('bwd_step_kernels.hpp', 'dzp.c = dh * (hp.c - ng.c) * zg.c * (1.0f - zg.c);',
+                     'dzp.c = dh * (hp.c - ng.c) * zg.c;'),
+    # the resident tail multiplies at most 4 of a wave's 16-k blocks: wrong from KB = 6 (H >= 256) on
+    'bwd_tail_four_blocks': ('bwd_step_kernels.hpp', 'if (i >= nmine) continue;   // wave-uniform',
+                             'if (i >= nmine || i >= 4) continue;'),
 }
 # the tests that must kill them (and pass on the product library)
-SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py', '-k',
+SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
+          'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_chain.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
-          'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle']
+          'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
+          'mixed_step_shapes or bptt_tail']
 
 
 def build(only=()):
@@ -76,9 +93,9 @@ def build(only=()):
     print('built', target)
 
 
-def run():
+def run(only=()):
   results = {}
-  for name in [None] + sorted(MUTANTS):
+  for name in [None] + sorted(m for m in MUTANTS if not only or m in only):
     env = dict(os.environ)
     if name:
       env['CMHSE_HIP_LIB'] = os.path.join(OUT, 'libcmhse_%s.so' % name)
@@ -98,10 +115,10 @@ def run():
     for l in res.stdout.splitlines():
       if 'Max absolute difference' in l or 'Mismatched elements' in l:
         print('      ', l.strip())
-  ok = results['product'][0] == 0 and all(results[m][1] for m in MUTANTS)
+  ok = results['product'][0] == 0 and all(results[m][1] for m in results if m != 'product')
   print('mutation check:', 'every mutant killed, product green' if ok else 'HOLE: see above')
   return 0 if ok else 1
 
 
 if __name__ == '__main__':
-  sys.exit(build(sys.argv[2:]) if sys.argv[1:2] == ['build'] else run())
+  sys.exit(build(sys.argv[2:]) if sys.argv[1:2] == ['build'] else run(sys.argv[2:]))
