@@ -1282,7 +1282,13 @@ extern "C" int cmhse_gru_pool_fwd_multi(const cmhse_gru_job* reqs, int32_t n_job
     const int rc = launch_attention(jobs[k], stream, jobs[k].sum_T, true);
     if (rc != CMHSE_OK) return rc;
   }
-  for (int k = 0; k < n_jobs; ++k) mark_ready(jobs[k], stream);     // (whatever was not final earlier)
+  // (whatever was not final earlier) on the stream where that output completes: a request on its
+  // own stream that is not joined back is final there, and nowhere on the caller's stream
+  for (int k = 0; k < n_jobs; ++k) {
+    hipStream_t own = jobs[k].own_stream;
+    const bool unjoined = own != nullptr && own != stream && (reqs[k].pool_mode & CMHSE_NO_JOIN) != 0;
+    mark_ready(jobs[k], unjoined ? own : stream);
+  }
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }
 

@@ -630,7 +630,8 @@ def gru_pool_fwd_multi(requests, tail_stream=None, job_streams=None, join=True, 
   must pass `hold`, a list that receives everything the queued work uses and that it keeps until
   that later join.  `ready_events`: one torch.cuda.Event (already recorded once, so that it owns a
   handle) or None per request; the call records it where that request's output becomes final
-  (cmhse_gru_job.out_ready_event) — early for a request whose chain ends while others still step."""
+  (cmhse_gru_job.out_ready_event) — early for a request whose chain ends while others still step, and
+  on its job stream for a request left un-joined (join=False)."""
   lib = _lib.load()
   if not 1 <= len(requests) <= MAX_JOBS:
     raise ValueError('gru_pool_fwd_multi takes 1..%d requests' % MAX_JOBS)
@@ -1163,6 +1164,20 @@ def _gru_pool_bwd_multi(requests, job_streams, join, hold, prepared):
     out.append((grads, dh0))
   rc = lib.cmhse_gru_pool_bwd_multi(jobs, len(requests), _stream())
   _lib.check(rc, 'cmhse_gru_pool_bwd_multi')
+  for k, r in enumerate(requests):
+    grads, dh0 = out[k]
+    sched = r['fctx']['sched']
+    if dh0 is None or r['fctx']['pool_mode'] != POOL_ALL:
+      continue
+    # all-states pooling: d h0 of sequence i is at its first output row (the row indexing of `out`,
+    # _prepare_bwd); the caller gets [S, H] in input order, gathered where the call's results are final
+    lens = np.empty(sched.S, dtype=np.int64)
+    lens[sched.order] = sched.lens_sorted
+    first = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    st = job_streams[k] if (not join and job_streams is not None) else torch.cuda.current_stream(dh0.device)
+    with torch.cuda.stream(st):
+      out[k] = (grads, dh0.index_select(0, torch.from_numpy(first).to(dh0.device)))
+    keep.append(dh0)
   if not join:
     hold.append(keep)
   return out
@@ -1189,7 +1204,11 @@ def _prepare_bwd(fctx, dout, dx_ptrs=None, d_emb_table=None, want_dh0=False):
   if dx_ptrs is not None:
     dx_dev = upload(np.asarray(dx_ptrs, dtype=np.uint64)[sched.order].view(np.int64).copy(),
                     device)
-  dh0 = torch.empty(S, H, dtype=torch.float32, device=device) if want_dh0 else None
+  # d h0 has the row indexing of `out` (cmhse_gru_pool_bwd): with all-states pooling a sequence's row
+  # is its first output row, so the buffer has sum_T rows (_gru_pool_bwd_multi gathers the S of them)
+  dh0 = None
+  if want_dh0:
+    dh0 = torch.empty(sched.sum_T if pool_mode == POOL_ALL else S, H, dtype=torch.float32, device=device)
   ws_bytes = lib.cmhse_gru_pool_bwd_workspace(S, sched.Tmax, sched.sum_T, I, H, pool_mode)
   ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
   return grads, dh0, g, dx_dev, ws, ws_bytes, dout

@@ -213,10 +213,11 @@ typedef struct cmhse_gru_job {
   void* out_ready_event; /* optional hipEvent_t (or NULL), recorded by the call where this request's
                           `out` becomes final: right behind its pooling pass when that is launched
                           early (tail_stream: its chain ended while other requests still step), else
-                          at the end of the call on `stream`.  A consumer on another stream — the
-                          device-to-host hand-over of evaluation.encode_data (evaluation.py:120-125) —
-                          waits on it instead of on the whole call, and so runs beside the other
-                          requests' remaining steps. */
+                          at the end of the call: on `stream`, or on this request's own `stream`
+                          when CMHSE_NO_JOIN leaves that un-joined (its output completes there).
+                          A consumer on another stream — the device-to-host hand-over of
+                          evaluation.encode_data (evaluation.py:120-125) — waits on it instead of on
+                          the whole call, and so runs beside the other requests' remaining steps. */
 } cmhse_gru_job;
 int cmhse_gru_pool_fwd_multi(const cmhse_gru_job* jobs, int32_t n_jobs, void* stream);
 
@@ -440,7 +441,9 @@ typedef struct cmhse_gru_grads {
  *                accumulated with float atomics: zero it first;
  *   d_emb_table  [vocab, I]: gradient of embed.weight, ACCUMULATED with float atomics (zero it
  *                first); token batches only (model.py:94);
- *   dh0          [S, H] (row indexing of `out`): d loss / d hidden (layers.py:98-100).
+ *   dh0          d loss / d hidden (layers.py:98-100) with the row indexing of `out`: sequence s
+ *                at row out_row[s] — [S, H], or [sum_T, H] with CMHSE_POOL_ALL, where out_row[s] is
+ *                the sequence's first output row.
  * Any of the three may be NULL; dx_rows and d_emb_table are mutually exclusive. */
 size_t cmhse_gru_pool_bwd_workspace(int32_t S, int32_t Tmax, int64_t sum_T, int32_t I, int32_t H,
                                     int32_t pool_mode);

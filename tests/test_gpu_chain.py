@@ -14,6 +14,7 @@ from gpu_common import (_blas_threads, _check_train_step_vs_oracle, _full_opt, _
                         _np_state_dicts, _plan_setup, _RecordForward, _robust_rank_rows)
 
 import bptt_shapes  # noqa: E402
+import fwd_shapes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -175,19 +176,19 @@ def test_resident_tails_fuzz(dev, seed, tune):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('pool,cls,H,S,n_long', [('attention', 'Attention', 32, 11, 13), ('maxout', 'Maxout', 48, 40, 13),
-                                                 ('seq2seq', 'Seq2Seq', 256, 23, 13), ('attention', 'Attention', 1024, 32, 13),
-                                                 ('maxout', 'Maxout', 64, 40, 29), ('attention', 'Attention', 1024, 32, 30)])
+@pytest.mark.parametrize('pool,cls,H,S,n_long', fwd_shapes.FWD_TAIL_CASES)
 def test_forward_tail_as_one_resident_kernel(dev, oracle, pool, cls, H, S, n_long, tune):
   """The few-sequence tail of a training chain's FORWARD pass inside one resident kernel
   (gru_fwd_tail_kernel: chains on a stream of their own, cmhse_gru_job.stream) against one launch
   per step (fwd_tail_min_steps = 0): outputs and every gradient (the kernel also writes the gate
   activations the backward pass consumes) equal to fp32 rounding, bitwise reproducible, and the
-  outputs against the float64 oracle."""
+  output and every gradient against the float64 oracle at every H.  The cases run every KB
+  instantiation (2, 4, 8 16-k blocks per wave: H = 32 ... 1024) with one and with two 16-row blocks
+  (tests/test_fwd_shapes_cpu.py)."""
   from cmhse_amd import layers, ops
   rng = np.random.RandomState(11 + H)
   I = 20 if H < 1024 else 64
-  T = 37
+  T = fwd_shapes.FWD_TAIL_T
   torch.manual_seed(9)
   layer = getattr(layers, cls)(I, H)
   with torch.no_grad():
@@ -195,10 +196,7 @@ def test_forward_tail_as_one_resident_kernel(dev, oracle, pool, cls, H, S, n_lon
     layer.rnn.bias_hh_l0.normal_(0, 0.1)
   sd = {'rnn.' + k: v.detach().numpy().astype(np.float64) for k, v in layer.state_dict().items()}
   layer = layer.to(dev)
-  lens = rng.randint(1, 9, size=S)
-  long_ones = rng.permutation(S)[:min(S, n_long)]   # n_long > 16: a tail of two 16-row blocks
-  lens[long_ones] = rng.randint(10, T + 1, size=len(long_ones))
-  lens[long_ones[0]] = T
+  lens = fwd_shapes.tail_case_lens(rng, S, n_long, T)   # n_long > 16: a tail of two 16-row blocks
   x = np.zeros((S, T, I), dtype=np.float32)
   for i, l in enumerate(lens):
     x[i, :l] = rng.standard_normal((l, I))
@@ -224,9 +222,15 @@ def test_forward_tail_as_one_resident_kernel(dev, oracle, pool, cls, H, S, n_lon
     assert float((a - b).abs().max()) <= 2e-5 * max(1e-6, float(a.abs().max()))
     assert torch.equal(b, c), 'not reproducible from run to run'
   assert float((per_step[0] - resident[0]).abs().max()) <= 2e-6 * float(per_step[0].abs().max())
-  if H <= 256:
-    want, _ = oracle.pooled_gru_forward_cache(pool, x, lens, sd, h0)
-    assert np.abs(resident[0].cpu().numpy() - want).max() <= 2e-5
+  with _blas_threads():
+    want, cache = oracle.pooled_gru_forward_cache(pool, x, lens, sd, h0)
+    grads, dx, dh0 = oracle.pooled_gru_backward(cache, w.astype(np.float64))
+  tag = '%s H%d S%d' % (pool, H, S)
+  assert np.abs(resident[0].cpu().numpy() - want).max() <= 2e-5, tag
+  grad_close(resident[1].cpu().numpy()[:, :dx.shape[1]], dx, tag + ' dx')
+  grad_close(resident[2].cpu().numpy(), dh0, tag + ' dh0')
+  for (pn, _), got in zip(layer.named_parameters(), resident[3:]):
+    grad_close(got.cpu().numpy(), grads['rnn.' + pn], tag + ' ' + pn)
 
 
 @pytest.mark.gpu

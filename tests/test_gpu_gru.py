@@ -276,6 +276,55 @@ def test_decoder_forward_matches_oracle(dev, oracle):
   assert_emb_close(y, want)
 
 
+def test_decoder_backward_with_initial_states_vs_oracle(dev, oracle):
+  """All-states pooling with initial states, trained: cmhse_gru_pool_bwd writes d h0 with the row
+  indexing of `out`, which for all-states pooling is each sequence's FIRST OUTPUT ROW (up to sum_T - 1),
+  not its index; ops gives it a buffer of sum_T rows and gathers the S rows in input order.  Every
+  gradient against the float64 oracle, twice, bit for bit (a [S, H] buffer was written out of bounds)."""
+  from cmhse_amd.decoder import Seq2Seq_Decode
+  rng = np.random.RandomState(12)
+  torch.manual_seed(5)
+  S, T, I, H = 30, 9, 20, 36
+  dec = Seq2Seq_Decode(I, H)
+  with torch.no_grad():
+    dec.rnn.bias_ih_l0.normal_(0, 0.1)
+    dec.rnn.bias_hh_l0.normal_(0, 0.1)
+  sd = {'rnn.' + k: v.detach().numpy().astype(np.float64) for k, v in dec.state_dict().items()}
+  dec = dec.to(dev)
+  lens = rng.randint(1, T + 1, size=S)
+  lens[0] = T
+  x = np.zeros((S, T, I), dtype=np.float32)
+  for i, l in enumerate(lens):
+    x[i, :l] = rng.standard_normal((l, I))
+  h0 = (0.5 * rng.standard_normal((S, H))).astype(np.float32)
+  w = rng.standard_normal((int(lens.sum()), H)).astype(np.float32)
+
+  def run():
+    dec.zero_grad()
+    xt = torch.from_numpy(x).to(dev).requires_grad_(True)
+    ht = torch.from_numpy(h0).to(dev).requires_grad_(True)
+    y = dec(xt, torch.from_numpy(lens), ht)
+    (y * torch.from_numpy(w).to(dev)).sum().backward()
+    torch.cuda.synchronize()
+    return [y.detach().clone(), xt.grad.clone(), ht.grad.clone()] + [p.grad.clone() for p in dec.parameters()]
+
+  first, again = run(), run()
+  for i, (a, b) in enumerate(zip(first, again)):
+    assert torch.equal(a, b), i
+  with _blas_threads():
+    c = oracle.gru_forward_cache(x, lens, sd, h0, np.float64)
+    starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    dhs = np.zeros_like(c['hs'])
+    for i, l in enumerate(lens):
+      dhs[i, :l] = w[starts[i]:starts[i] + l]
+    grads, dx, dh0 = oracle.gru_backward(c, dhs)
+  assert_emb_close(first[0].cpu().numpy(), np.concatenate([c['hs'][i, :l] for i, l in enumerate(lens)]))
+  grad_close(first[1].cpu().numpy()[:, :dx.shape[1]], dx, 'dx')
+  grad_close(first[2].cpu().numpy(), dh0, 'dh0')
+  for (pn, _), got in zip(dec.named_parameters(), first[3:]):
+    grad_close(got.cpu().numpy(), grads['rnn.' + pn], pn)
+
+
 @pytest.mark.parametrize('pool', ['attention', 'maxout', 'seq2seq'])
 @pytest.mark.parametrize('S,T,I,H', [(2300, 5, 36, 72), (2200, 3, 500, 128), (2100, 4, 12, 64), (2100, 3, 20, 96)])
 def test_bf16x3_mode_vs_oracle(dev, oracle, pool, S, T, I, H):
@@ -381,6 +430,44 @@ def test_gru_pool_fwd_multi_equals_separate_calls(dev):
   assert lib.cmhse_gru_pool_fwd_multi(jobs, _lib.MAX_JOBS + 1, None) == -1
   assert lib.cmhse_gru_pool_fwd_multi(jobs, 1, None) == -1          # null request fields
   assert lib.cmhse_gru_pool_fwd_multi(None, 1, None) == -1
+
+
+@pytest.mark.parametrize('pool', ['LAST', 'MAX'])
+def test_ready_event_of_an_unjoined_job_stream_request(dev, pool):
+  """out_ready_event of a request on its own stream left un-joined (job_streams, join=False) is
+  recorded on that stream, where its output completes — not on the caller's stream, which is never
+  ordered behind it.  The job stream is held back by a sleep queued in front of the call and `out`
+  starts as NaN: a consumer that waits for the event reads exactly what a joined call computes."""
+  from cmhse_amd import ops
+  rng = np.random.RandomState(31)
+  g = torch.Generator().manual_seed(8)
+  S, T, I, H = 40, 9, 24, 64
+  weights = {k: v.to(dev) for k, v in dict(
+      w_ih=torch.randn(3 * H, I, generator=g).mul_(0.2), w_hh=torch.randn(3 * H, H, generator=g).mul_(0.2),
+      b_ih=torch.randn(3 * H, generator=g).mul_(0.1), b_hh=torch.randn(3 * H, generator=g).mul_(0.1)).items()}
+  lens = rng.randint(1, T + 1, size=S).astype(np.int64)
+  lens[0] = T
+  x = torch.randn(S, T, I, generator=g).to(dev)
+  req = dict(weights=weights, pool_mode=getattr(ops, 'POOL_' + pool), lens=lens, I=I, H=H, device=dev,
+             x_ptrs=ops.padded_row_ptrs(x))
+  want = ops.gru_pool_fwd_multi([req], job_streams=[ops.stream_set(dev)[0]])[0][0].clone()
+  torch.cuda.synchronize()
+  job_stream, consumer = ops.stream_set(dev)[0], torch.cuda.Stream(dev)
+  out = torch.full((S, H), float('nan'), device=dev)
+  ready = torch.cuda.Event()
+  ready.record()
+  torch.cuda.synchronize()
+  with torch.cuda.stream(job_stream):
+    torch.cuda._sleep(50 * 1000 * 1000)    # tens of ms: the steps queue behind it
+  hold = []
+  ops.gru_pool_fwd_multi([dict(req, out=out)], job_streams=[job_stream], join=False, hold=hold,
+                         ready_events=[ready])
+  with torch.cuda.stream(consumer):
+    consumer.wait_event(ready)
+    seen = out.clone()
+  torch.cuda.synchronize()
+  assert not torch.isnan(seen).any(), 'the ready event fired before the output was written'
+  assert torch.equal(seen, want)
 
 
 @pytest.mark.parametrize('I', [24, 7])

@@ -16,6 +16,9 @@ Mutants:
   bwd_step_combine_4_waves, bwd_step_drops_carry, bwd_gates_dz, bwd_tail_four_blocks   the BPTT step
                  shapes (killed by tests/test_gpu_bptt_shapes.py; the tail one by test_gpu_chain.py's
                  resident-tail test)
+  fwd_tail_two_blocks, mid_combine_4_waves, tiny_all_prev_state, tile_all_prev_state, scalar_k_remainder
+                 the forward step shapes (killed by tests/test_gpu_fwd_shapes.py; the tail one by
+                 test_gpu_chain.py's forward resident-tail test)
 """
 import os
 import shutil
@@ -59,13 +62,29 @@ MUTANTS = {
     # the resident tail multiplies at most 4 of a wave's 16-k blocks: wrong from KB = 6 (H >= 256) on
     'bwd_tail_four_blocks': ('bwd_step_kernels.hpp', 'if (i >= nmine) continue;   // wave-uniform',
                              'if (i >= nmine || i >= 4) continue;'),
+    # forward step shapes (tests/test_gpu_fwd_shapes.py): value-only edits as above.
+    # The forward resident tail multiplies at most 2 of a wave's 16-k blocks: wrong from KB = 4 (H > 256) on
+    'fwd_tail_two_blocks': ('gru_small_batch.hpp', 'if (i >= nmine) continue;   // wave-uniform',
+                            'if (i >= nmine || i >= 2) continue;'),
+    # the mid-size step combines one K slice per wave: wrong for its 4-wave forms (two slices per wave)
+    'mid_combine_4_waves': ('gru_small_batch.hpp', 'for (int w = 0; w < kMidSlices; ++w)\n          hg[g] +=',
+                            'for (int w = 0; w < NW; ++w)\n          hg[g] +='),
+    # the latency-shaped step's all-states epilogue stores the previous state (gru_step_tiny_kernel)
+    'tiny_all_prev_state': ('gru_small_batch.hpp', '\n    p.out[(static_cast<int64_t>(p.out_row[em]) + p.t) * H + u] = hn;',
+                            '\n    p.out[(static_cast<int64_t>(p.out_row[em]) + p.t) * H + u] = hp;'),
+    # ... and that of the LDS-tiled step and the step chain (gru_step_tile.hpp)
+    'tile_all_prev_state': ('gru_step_tile.hpp', 'out[(static_cast<int64_t>(orow[i]) + t) * H + u] = v;',
+                            'out[(static_cast<int64_t>(orow[i]) + t) * H + u] = hp[r4 + i];'),
+    # the scalar-load tile loops keep the 4th element of a k group past K (its load is clamped to the
+    # row's last element, so the value is that element instead of 0)
+    'scalar_k_remainder': ('nt_core.hpp', 'v.w = (valid && k + 3 < klim) ? v.w : 0.f;', 'v.w = valid ? v.w : 0.f;'),
 }
 # the tests that must kill them (and pass on the product library)
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
-          'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_chain.py', '-k',
+          'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
           'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
-          'mixed_step_shapes or bptt_tail']
+          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail']
 
 
 def build(only=()):
