@@ -62,8 +62,15 @@ GROUP_MEAN, GROUP_MAX = 0, 1     # CMHSE_GROUP_MEAN / CMHSE_GROUP_MAX
 GROUP_TILE_ROWS = 128   # CMHSE_GROUP_TILE_ROWS: the longest video / paragraph cmhse_group_plan packs
 
 
+GROUP_P2V, GROUP_V2P = 0, 1      # CMHSE_GROUP_P2V / CMHSE_GROUP_V2P
+
+
 def group_plan_max(B):
   return 4 * B + 9      # CMHSE_GROUP_PLAN_MAX(B)
+
+
+def group_topk_plan_max(Bv, Bp):
+  return 2 * Bv + 2 * Bp + 12      # CMHSE_GROUP_TOPK_PLAN_MAX(Bv, Bp)
 
 
 class StepLosses(ctypes.Structure):
@@ -112,6 +119,12 @@ SIGNATURES = {
     'cmhse_group_rank': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                         c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cmhse_group_topk_plan': (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                        c_int32]),
+    'cmhse_group_topk_workspace': (c_size_t, [c_void_p, c_int32]),
+    'cmhse_group_topk': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                        c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_size_t, c_void_p]),
     'cmhse_cosine_sim': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                         c_void_p]),
     'cmhse_contrastive_workspace': (c_size_t, [c_int32]),

@@ -21,6 +21,15 @@
 //                       (paragraph -> video) the count of entries above the diagonal and the top-1 key
 //                       (score_tile.hpp's score key), one partial per tile;
 //   group_rank_final_kernel   sums / maxes the partials of each row and column.
+//
+// Group-wise top-K (cmhse_group_topk: any video set against any paragraph set, either way round):
+//   cmhse_group_topk_plan     host only: the gallery side packed as above, the query side also capped
+//                             at gt_qcap(K) groups a tile (the LDS of its lists);
+//   group_topk_select_kernel  query tiles x gallery panels: group_sim_kernel's tile loop and block
+//                             reduction (group_tile_reduce, shared) with a top-K epilogue — a ballot
+//                             against each query's K-th key, wave_merge (topk_lists.hpp) into its
+//                             sorted list in LDS, the panel's lists to the workspace at the end;
+//   group_topk_merge_kernel   merge_panel_lists (topk_lists.hpp): the panels' lists of each query.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +37,7 @@
 #include "../../include/cmhse_hip.h"
 #include "nt_core.hpp"
 #include "score_tile.hpp"
+#include "topk_lists.hpp"
 
 namespace cmhse {
 namespace {
@@ -63,42 +73,19 @@ struct GroupParams {
   float* G;                // [B, B]
 };
 
-template <bool VEC>
-__global__ __launch_bounds__(kThreads) void group_sim_kernel(const GroupParams p) {
+// The (video, paragraph) blocks of one clip x caption tile, reduced from the accumulators nt_phase
+// left (acc[2][2]: the wave's 64 x 64 quarter of the 128 x 128 tile) — the epilogue of
+// group_sim_kernel and group_topk_select_kernel, called after nt_phase's closing barrier.  nv videos
+// of nr clip rows, nq paragraphs; my_voff / my_poff: thread t <= nv / nq holds local offset t.  The
+// scores are staged in two 64-row halves in the freed tile buffers and each block is reduced by one
+// thread, clip-major then caption; a block whose video straddles the halves carries its running fp64
+// sum (and max) across in LDS, which keeps the order.  sink(v, q, value) receives each block's value
+// once (local video, local paragraph).  Ends with a barrier: the stage is free, every value sunk.
+template <typename Sink>
+__device__ __forceinline__ void group_tile_reduce(float* smem, const f32x16 (&acc)[2][2], int nv, int nq, int nr,
+                                                  int my_voff, int my_poff, int use_max, Sink sink) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, srow = tid >> 2;
-  int rt, ct;
-  if (p.group > 0) {
-    // a caption tile crosses the fabric once per group, the group's clip tiles stay L2-resident
-    const TileIdx t = xcd_deal_tile(blockIdx.x, p.group, p.col_tiles);
-    rt = t.rt;
-    ct = t.ct;
-    if (rt >= p.row_tiles) return;   // padding of the last row group / the grid
-  } else {
-    rt = blockIdx.x / p.col_tiles;
-    ct = blockIdx.x % p.col_tiles;
-  }
-  const int v0 = p.rt_vid[rt], nv = p.rt_vid[rt + 1] - v0;
-  const int q0 = p.ct_par[ct], nq = p.ct_par[ct + 1] - q0;
-  const int r_begin = p.clip_off[v0], nr = p.clip_off[v0 + nv] - r_begin;
-  const int c_begin = p.cap_off[q0], nc = p.cap_off[q0 + nq] - c_begin;
-  // the tile's local video / paragraph offsets, loaded in front of the K loop (they go to LDS once
-  // the tile buffers are free); nv, nq <= 128 (every video / paragraph has a row)
-  const int my_voff = (tid <= nv) ? p.clip_off[v0 + tid] - r_begin : 0;
-  const int my_poff = (tid <= nq) ? p.cap_off[q0 + tid] - c_begin : 0;
-
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  rowaddr_t ar[kGrBM / 64], br[kGrBN / 64];
-  bool av[kGrBM / 64], bv[kGrBN / 64];
-#pragma unroll
-  for (int i = 0; i < kGrBM / 64; ++i) ar[i] = tile_row(p.C, p.D, r_begin, srow + 64 * i, nr, &av[i]);
-#pragma unroll
-  for (int i = 0; i < kGrBN / 64; ++i) br[i] = tile_row(p.S, p.D, c_begin, srow + 64 * i, nc, &bv[i]);
-  f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
-  const int b_row0[2] = {wn * 64, wn * 64 + 32};
-  // ends with a barrier: every wave is done with the tile buffers
-  nt_phase<kGrBM, kGrBN, 2, 2, 2, 1, VEC>(smem, ar, av, br, bv, p.D, wm * 64, b_row0, acc);
-
+  const int wm = wave >> 1, wn = wave & 1;
   char* lds = reinterpret_cast<char*>(smem);
   float* stage = smem;
   double* carry = reinterpret_cast<double*>(lds + kGrCarryOff);
@@ -137,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void group_sim_kernel(const GroupParams p
       const int lo = rs > h0 ? rs : h0, hi = re < h1 ? re : h1;
       const int cs = s_poff[q], ce = s_poff[q + 1];
       const bool cont = rs < h0;                    // started in the previous pass
-      if (p.use_max) {
+      if (use_max) {
         float m = cont ? cmax[q] : -INFINITY;
         for (int r = lo; r < hi; ++r) {
           const float* srow_ = stage + (r - h0) * kGrLd;
@@ -147,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void group_sim_kernel(const GroupParams p
           }
         }
         if (re > h1) cmax[q] = m;
-        else p.G[static_cast<int64_t>(v0 + v) * p.B + q0 + q] = m;
+        else sink(v, q, m);
       } else {
         double sum = cont ? carry[q] : 0.0;
         for (int r = lo; r < hi; ++r) {
@@ -155,9 +142,7 @@ __global__ __launch_bounds__(kThreads) void group_sim_kernel(const GroupParams p
           for (int c = cs; c < ce; ++c) sum += static_cast<double>(srow_[c]);
         }
         if (re > h1) carry[q] = sum;
-        else
-          p.G[static_cast<int64_t>(v0 + v) * p.B + q0 + q] =
-              static_cast<float>(sum / static_cast<double>((re - rs) * (ce - cs)));
+        else sink(v, q, static_cast<float>(sum / static_cast<double>((re - rs) * (ce - cs))));
       }
       v += step_v;
       q += step_q;
@@ -168,6 +153,154 @@ __global__ __launch_bounds__(kThreads) void group_sim_kernel(const GroupParams p
     }
     __syncthreads();   // every thread is done with the stage (and has written its carries)
   }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void group_sim_kernel(const GroupParams p) {
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, srow = tid >> 2;
+  int rt, ct;
+  if (p.group > 0) {
+    // a caption tile crosses the fabric once per group, the group's clip tiles stay L2-resident
+    const TileIdx t = xcd_deal_tile(blockIdx.x, p.group, p.col_tiles);
+    rt = t.rt;
+    ct = t.ct;
+    if (rt >= p.row_tiles) return;   // padding of the last row group / the grid
+  } else {
+    rt = blockIdx.x / p.col_tiles;
+    ct = blockIdx.x % p.col_tiles;
+  }
+  const int v0 = p.rt_vid[rt], nv = p.rt_vid[rt + 1] - v0;
+  const int q0 = p.ct_par[ct], nq = p.ct_par[ct + 1] - q0;
+  const int r_begin = p.clip_off[v0], nr = p.clip_off[v0 + nv] - r_begin;
+  const int c_begin = p.cap_off[q0], nc = p.cap_off[q0 + nq] - c_begin;
+  // the tile's local video / paragraph offsets, loaded in front of the K loop (they go to LDS once
+  // the tile buffers are free); nv, nq <= 128 (every video / paragraph has a row)
+  const int my_voff = (tid <= nv) ? p.clip_off[v0 + tid] - r_begin : 0;
+  const int my_poff = (tid <= nq) ? p.cap_off[q0 + tid] - c_begin : 0;
+
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  rowaddr_t ar[kGrBM / 64], br[kGrBN / 64];
+  bool av[kGrBM / 64], bv[kGrBN / 64];
+#pragma unroll
+  for (int i = 0; i < kGrBM / 64; ++i) ar[i] = tile_row(p.C, p.D, r_begin, srow + 64 * i, nr, &av[i]);
+#pragma unroll
+  for (int i = 0; i < kGrBN / 64; ++i) br[i] = tile_row(p.S, p.D, c_begin, srow + 64 * i, nc, &bv[i]);
+  f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
+  const int b_row0[2] = {wn * 64, wn * 64 + 32};
+  // ends with a barrier: every wave is done with the tile buffers
+  nt_phase<kGrBM, kGrBN, 2, 2, 2, 1, VEC>(smem, ar, av, br, bv, p.D, wm * 64, b_row0, acc);
+  group_tile_reduce(smem, acc, nv, nq, nr, my_voff, my_poff, p.use_max, [&](int v, int q, float g) {
+    p.G[static_cast<int64_t>(v0 + v) * p.B + q0 + q] = g;
+  });
+}
+
+// ---- group-wise top-K (cmhse_group_topk) ----------------------------------------------------------
+// The query side is a clip row tile (v2p) or a caption column tile (p2v); the MFMA tile stays clips x
+// captions either way, so group_tile_reduce's clip-major order holds for both directions.  LDS of a
+// workgroup: the 40 KB tile buffers (the reduction's stage too), one 128-key candidate buffer per
+// wave, then per query group its running list (K keys) and a row of block scores of the current
+// gallery tile (at most 128 groups: every group has a row), for at most qcap(K) query groups.
+constexpr int kGtGalleryMax = kGrBN;                       // groups of a gallery tile, at most
+constexpr int kGtBlkLd = kGtGalleryMax + 1;                // block score row stride (floats)
+constexpr size_t kGtCandOff = kGrSmem;                     // score_key_t [4 waves][128]
+constexpr size_t kGtListOff = kGtCandOff + sizeof(score_key_t) * kGtGalleryMax * (kThreads / 64);
+constexpr int kGtHdr = 8;                                  // Bv, Bp, Nc, Ns, direction, K, R, C
+constexpr int kGtQcapMax = 64;
+constexpr int kGtCUs = 256;                                // MI355X compute units
+constexpr size_t kGtLdsPerCU = 160 * 1024;
+
+struct GroupTopkParams {
+  const float* C;          // [Nc, D] clip rows
+  const float* S;          // [Ns, D] caption rows
+  int32_t D, use_max, p2v, K;
+  int32_t Bq;              // query groups
+  int32_t q_tiles, g_tiles, panels;
+  const int32_t* clip_off; // [Bv + 1] (device copy of the plan)
+  const int32_t* cap_off;  // [Bp + 1]
+  const int32_t* rt_vid;   // [R + 1] first video of each clip tile
+  const int32_t* ct_par;   // [C + 1] first paragraph of each caption tile
+  score_key_t* ws;         // [panels, Bq, K] sorted keys of each panel
+};
+
+// Grid: query tiles x gallery PANELS (runs of gallery tiles), panel-major, dealt to the XCDs in
+// contiguous runs as topk_select_kernel's: the query tiles of a panel stream its gallery tiles
+// through one L2.  Per gallery tile: nt_phase, the block reduction into blk [query][gallery], then
+// each wave takes every fourth query group: a ballot of key > the query's K-th key picks the
+// candidates, wave_merge adds them to its list.  The panel's lists go to the workspace.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void group_topk_select_kernel(const GroupTopkParams p) {
+  const int per_xcd = static_cast<int>(gridDim.x >> 3);
+  const int L = static_cast<int>(blockIdx.x & 7) * per_xcd + static_cast<int>(blockIdx.x >> 3);
+  if (L >= p.q_tiles * p.panels) return;   // padding of the grid to a multiple of 8
+  const int panel = L / p.q_tiles, qt = L % p.q_tiles;
+  const int t_begin = static_cast<int>(static_cast<int64_t>(panel) * p.g_tiles / p.panels);
+  const int t_end = static_cast<int>(static_cast<int64_t>(panel + 1) * p.g_tiles / p.panels);
+  const int K = p.K;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, srow = tid >> 2;
+  const int32_t* q_start = p.p2v ? p.ct_par : p.rt_vid;
+  const int32_t* g_start = p.p2v ? p.rt_vid : p.ct_par;
+  const int qg0 = q_start[qt], nQ = q_start[qt + 1] - qg0;   // nQ <= qcap(K): the plan is checked
+
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  char* lds = reinterpret_cast<char*>(smem);
+  score_key_t* cand = reinterpret_cast<score_key_t*>(lds + kGtCandOff) + wave * kGtGalleryMax;
+  score_key_t* lists = reinterpret_cast<score_key_t*>(lds + kGtListOff);   // [nQ][K]
+  float* blk = reinterpret_cast<float*>(lds + kGtListOff + sizeof(score_key_t) * nQ * K);   // [nQ][kGtBlkLd]
+  for (int e = tid; e < nQ * K; e += kThreads) lists[e] = 0ull;   // (seen after nt_phase's barriers)
+
+  const int b_row0[2] = {wn * 64, wn * 64 + 32};
+  for (int t = t_begin; t < t_end; ++t) {
+    const int gg0 = g_start[t], nG = g_start[t + 1] - gg0;
+    const int v0 = p.p2v ? gg0 : qg0, nv = p.p2v ? nG : nQ;
+    const int q0 = p.p2v ? qg0 : gg0, nq = p.p2v ? nQ : nG;
+    const int r_begin = p.clip_off[v0], nr = p.clip_off[v0 + nv] - r_begin;
+    const int c_begin = p.cap_off[q0], nc = p.cap_off[q0 + nq] - c_begin;
+    const int my_voff = (tid <= nv) ? p.clip_off[v0 + tid] - r_begin : 0;
+    const int my_poff = (tid <= nq) ? p.cap_off[q0 + tid] - c_begin : 0;
+    rowaddr_t ar[kGrBM / 64], br[kGrBN / 64];
+    bool av[kGrBM / 64], bv[kGrBN / 64];
+#pragma unroll
+    for (int i = 0; i < kGrBM / 64; ++i) ar[i] = tile_row(p.C, p.D, r_begin, srow + 64 * i, nr, &av[i]);
+#pragma unroll
+    for (int i = 0; i < kGrBN / 64; ++i) br[i] = tile_row(p.S, p.D, c_begin, srow + 64 * i, nc, &bv[i]);
+    f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
+    // ends with a barrier: every wave is done with the tile buffers (and with the previous tile's
+    // selection, so blk is free)
+    nt_phase<kGrBM, kGrBN, 2, 2, 2, 1, VEC>(smem, ar, av, br, bv, p.D, wm * 64, b_row0, acc);
+    const bool p2v = p.p2v;
+    group_tile_reduce(smem, acc, nv, nq, nr, my_voff, my_poff, p.use_max, [&](int v, int q, float g) {
+      blk[p2v ? q * kGtBlkLd + v : v * kGtBlkLd + q] = g;
+    });
+    for (int qi = wave; qi < nQ; qi += kThreads / 64) {   // (wave-uniform)
+      score_key_t* lst = lists + qi * K;
+      const score_key_t thr = lst[K - 1];
+      const float* row = blk + qi * kGtBlkLd;
+      const score_key_t k0 = lane < nG ? score_key(row[lane], gg0 + lane) : 0ull;
+      const score_key_t k1 = lane + 64 < nG ? score_key(row[lane + 64], gg0 + lane + 64) : 0ull;
+      const bool c0 = k0 > thr, c1 = k1 > thr;
+      const unsigned long long m0 = __ballot(c0), m1 = __ballot(c1);
+      if ((m0 | m1) == 0ull) continue;
+      const unsigned long long below = (1ull << lane) - 1ull;
+      if (c0) cand[__popcll(m0 & below)] = k0;
+      if (c1) cand[__popcll(m0) + __popcll(m1 & below)] = k1;
+      __builtin_amdgcn_wave_barrier();
+      wave_merge(lst, K, cand, __popcll(m0) + __popcll(m1), lane);
+    }
+  }
+  __syncthreads();
+  score_key_t* out = p.ws + (static_cast<int64_t>(panel) * p.Bq + qg0) * K;
+  for (int e = tid; e < nQ * K; e += kThreads) out[e] = lists[e];
+}
+
+__global__ __launch_bounds__(kThreads) void group_topk_merge_kernel(const PanelLists p) {
+  __shared__ score_key_t s_list[kThreads / 64][CMHSE_TOPK_MAX];
+  __shared__ score_key_t s_cand[kThreads / 64][CMHSE_TOPK_MAX];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = blockIdx.x * (kThreads / 64) + wave;
+  if (li >= p.nrows) return;   // (no barrier below)
+  merge_panel_lists(p, li, s_list[wave], s_cand[wave], lane);
 }
 
 struct GroupRankParams {
@@ -270,11 +403,14 @@ bool offsets_ok(const int32_t* off, int32_t B) {
   return true;
 }
 
-// the plan's tile starts: [0, ..., B], strictly increasing, every tile's rows <= cap
-bool tiles_ok(const int32_t* start, int32_t T, const int32_t* off, int32_t B, int cap) {
+// the plan's tile starts: [0, ..., B], strictly increasing, every tile's rows <= cap and groups
+// <= max_groups
+bool tiles_ok(const int32_t* start, int32_t T, const int32_t* off, int32_t B, int cap,
+              int32_t max_groups = 0x7fffffff) {
   if (T < 1 || T > B || start[0] != 0 || start[T] != B) return false;
   for (int32_t t = 0; t < T; ++t)
-    if (start[t + 1] <= start[t] || off[start[t + 1]] - off[start[t]] > cap) return false;
+    if (start[t + 1] <= start[t] || off[start[t + 1]] - off[start[t]] > cap || start[t + 1] - start[t] > max_groups)
+      return false;
   return true;
 }
 
@@ -293,19 +429,81 @@ bool plan_ok(const int32_t* ph, int32_t plan_len_, int32_t B, int32_t Nc, int32_
          tiles_ok(rt, R, clip_off, B, kGrBM) && tiles_ok(ctp, Cc, cap_off, B, kGrBN);
 }
 
-// greedy packing of whole groups (in order) into tiles of at most `cap` rows; returns the tile count
-int32_t pack(const int32_t* off, int32_t B, int cap, int32_t* start) {
+// greedy packing of whole groups (in order) into tiles of at most `cap` rows and `max_groups`
+// groups; returns the tile count
+int32_t pack(const int32_t* off, int32_t B, int cap, int32_t* start, int32_t max_groups = 0x7fffffff) {
   int32_t T = 0;
   start[T++] = 0;
   int32_t first = 0;
   for (int32_t b = 1; b < B; ++b)
-    if (off[b + 1] - off[first] > cap) {
+    if (off[b + 1] - off[first] > cap || b - first >= max_groups) {
       start[T++] = b;
       first = b;
     }
   start[T] = B;
   return T;
 }
+
+// Query groups per query tile at K: as many as leave two workgroups' LDS per CU (the occupancy the
+// GEMM keeps most of its rate at), in multiples of 8, at most 64; where that would be fewer than 32
+// (K > 72), one workgroup per CU with 64.  K = 1 / 10 / 50 / 128: 64 / 56 / 40 / 64 query groups,
+// 77 / 77 / 80 / 140 KB of LDS, 2 / 2 / 2 / 1 workgroups per CU.
+int32_t gt_qcap(int32_t K) {
+  const size_t per_q = sizeof(score_key_t) * K + sizeof(float) * kGtBlkLd;
+  int32_t q = static_cast<int32_t>((kGtLdsPerCU / 2 - kGtListOff) / per_q) / 8 * 8;
+  if (q < 32) q = static_cast<int32_t>((kGtLdsPerCU - kGtListOff) / per_q) / 8 * 8;
+  return q > kGtQcapMax ? kGtQcapMax : q;
+}
+
+size_t gt_smem(int32_t K) {
+  return kGtListOff + (sizeof(score_key_t) * K + sizeof(float) * kGtBlkLd) * static_cast<size_t>(gt_qcap(K));
+}
+
+// Panels per query tile, never more than there are gallery tiles.  Equal workgroups (a panel's share
+// of the gallery each) run in rounds of `slots` resident ones, so a launch takes rounds / P panel
+// lengths; from P0, the count that fills the slots once, up to 4 P0 + 3, a larger P is taken when it
+// takes at least 10 % fewer (more panels: more workspace, more merging, more warm-up tiles).  At val_1
+// (~140 query tiles) P0 is 1 at K = 128 (256 slots: over 100 CUs idle) and 3 at K = 50 (512 slots,
+// ~420 busy); P = 7 runs both in nearly whole rounds.  The count depends on the query tiles and K
+// only — it does not grow with the gallery, nor does the workspace.
+int32_t gt_panels(int32_t q_tiles, int32_t g_tiles, int32_t K) {
+  int per_cu = static_cast<int>(kGtLdsPerCU / gt_smem(K));
+  per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
+  const int64_t slots = static_cast<int64_t>(kGtCUs) * per_cu;
+  const int64_t P0 = slots / q_tiles < 1 ? 1 : slots / q_tiles;
+  int64_t best = P0, best_rounds = (q_tiles * P0 + slots - 1) / slots;
+  for (int64_t P = P0 + 1; P <= 4 * P0 + 3; ++P) {
+    const int64_t rounds = (q_tiles * P + slots - 1) / slots;
+    if (10 * rounds * best < 9 * best_rounds * P) {   // rounds / P < 0.9 best_rounds / best
+      best = P;
+      best_rounds = rounds;
+    }
+  }
+  return static_cast<int32_t>(best < g_tiles ? best : g_tiles);
+}
+
+int64_t gt_plan_len(int64_t Bv, int64_t Bp, int64_t R, int64_t Cc) { return kGtHdr + Bv + Bp + R + Cc + 4; }
+
+// The host top-K plan checked in full (O(Bv + Bp)) against the call: what the kernels trust — tile
+// rows within the tile buffers, query groups per tile within the LDS lists.
+bool gt_plan_ok(const int32_t* ph, int32_t len, int32_t Nc, int32_t Ns, int32_t direction, int32_t K) {
+  if (!ph || len < kGtHdr) return false;
+  const int32_t Bv = ph[0], Bp = ph[1], R = ph[6], Cc = ph[7];
+  if (Bv < 1 || Bp < 1 || ph[2] != Nc || ph[3] != Ns || ph[4] != direction || ph[5] != K) return false;
+  if (direction != CMHSE_GROUP_P2V && direction != CMHSE_GROUP_V2P) return false;
+  const int32_t Bg = direction == CMHSE_GROUP_P2V ? Bv : Bp;
+  if (K < 1 || K > CMHSE_TOPK_MAX || K > Bg) return false;
+  if (R < 1 || R > Bv || Cc < 1 || Cc > Bp || len != gt_plan_len(Bv, Bp, R, Cc)) return false;
+  const int32_t* clip_off = ph + kGtHdr;
+  const int32_t* cap_off = clip_off + Bv + 1;
+  const int32_t* rt = cap_off + Bp + 1;
+  const int32_t* ctp = rt + R + 1;
+  const int32_t qcap = gt_qcap(K);
+  return offsets_ok(clip_off, Bv) && offsets_ok(cap_off, Bp) && clip_off[Bv] == Nc && cap_off[Bp] == Ns &&
+         tiles_ok(rt, R, clip_off, Bv, kGrBM, direction == CMHSE_GROUP_V2P ? qcap : 0x7fffffff) &&
+         tiles_ok(ctp, Cc, cap_off, Bp, kGrBN, direction == CMHSE_GROUP_P2V ? qcap : 0x7fffffff);
+}
+
 
 bool group_args_ok(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D, int32_t B,
                    const int32_t* plan_host, const int32_t* plan, int32_t plan_len_, int32_t reduce) {
@@ -418,5 +616,86 @@ extern "C" int cmhse_group_rank(const float* clips, const float* caps, int32_t N
   if (rc != CMHSE_OK) return rc;
   hipLaunchKernelGGL(group_rank_kernel, dim3(static_cast<unsigned>(tiles * tiles)), dim3(kThreads), 0, stream, rp);
   hipLaunchKernelGGL(group_rank_final_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, stream, rp);
+  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
+}
+
+extern "C" int32_t cmhse_group_topk_plan(const int32_t* clip_off_host, int32_t Bv, const int32_t* cap_off_host,
+                                         int32_t Bp, int32_t direction, int32_t K, int32_t* plan, int32_t plan_cap) {
+  if (!clip_off_host || !cap_off_host || !plan || Bv <= 0 || Bp <= 0) return CMHSE_ERR_ARG;
+  if (direction != CMHSE_GROUP_P2V && direction != CMHSE_GROUP_V2P) return CMHSE_ERR_ARG;
+  const int32_t Bg = direction == CMHSE_GROUP_P2V ? Bv : Bp;
+  if (K < 1 || K > CMHSE_TOPK_MAX || K > Bg) return CMHSE_ERR_ARG;
+  if (!offsets_ok(clip_off_host, Bv) || !offsets_ok(cap_off_host, Bp)) return CMHSE_ERR_ARG;
+  for (int32_t b = 0; b < Bv; ++b)
+    if (clip_off_host[b + 1] - clip_off_host[b] > kGrBM) return CMHSE_ERR_UNSUPPORTED;
+  for (int32_t b = 0; b < Bp; ++b)
+    if (cap_off_host[b + 1] - cap_off_host[b] > kGrBN) return CMHSE_ERR_UNSUPPORTED;
+  if (plan_cap < gt_plan_len(Bv, Bp, Bv, Bp)) return CMHSE_ERR_WORKSPACE;   // CMHSE_GROUP_TOPK_PLAN_MAX
+  plan[0] = Bv;
+  plan[1] = Bp;
+  plan[2] = clip_off_host[Bv];
+  plan[3] = cap_off_host[Bp];
+  plan[4] = direction;
+  plan[5] = K;
+  int32_t* clip_off = plan + kGtHdr;
+  int32_t* cap_off = clip_off + Bv + 1;
+  for (int32_t b = 0; b <= Bv; ++b) clip_off[b] = clip_off_host[b];
+  for (int32_t b = 0; b <= Bp; ++b) cap_off[b] = cap_off_host[b];
+  const int32_t qcap = gt_qcap(K);
+  int32_t* rt = cap_off + Bp + 1;
+  const int32_t R = pack(clip_off, Bv, kGrBM, rt, direction == CMHSE_GROUP_V2P ? qcap : 0x7fffffff);
+  const int32_t Cc = pack(cap_off, Bp, kGrBN, rt + R + 1, direction == CMHSE_GROUP_P2V ? qcap : 0x7fffffff);
+  plan[6] = R;
+  plan[7] = Cc;
+  return static_cast<int32_t>(gt_plan_len(Bv, Bp, R, Cc));
+}
+
+extern "C" size_t cmhse_group_topk_workspace(const int32_t* plan_host, int32_t plan_len_) {
+  if (!plan_host || plan_len_ < kGtHdr ||
+      !gt_plan_ok(plan_host, plan_len_, plan_host[2], plan_host[3], plan_host[4], plan_host[5]))
+    return 0;
+  const bool p2v = plan_host[4] == CMHSE_GROUP_P2V;
+  const int32_t Bq = p2v ? plan_host[1] : plan_host[0], K = plan_host[5];
+  const int32_t q_tiles = p2v ? plan_host[7] : plan_host[6], g_tiles = p2v ? plan_host[6] : plan_host[7];
+  return align256(static_cast<size_t>(gt_panels(q_tiles, g_tiles, K)) * static_cast<size_t>(Bq) *
+                  static_cast<size_t>(K) * sizeof(score_key_t));
+}
+
+extern "C" int cmhse_group_topk(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                                const int32_t* plan_host, const int32_t* plan, int32_t plan_len_, int32_t direction,
+                                int32_t reduce, int32_t K, float* scores, int32_t* index, void* workspace,
+                                size_t workspace_bytes, void* stream_) {
+  if (!clips || !caps || !plan_host || !plan || !scores || !index || !workspace) return CMHSE_ERR_ARG;
+  if (Nc <= 0 || Ns <= 0 || D <= 0) return CMHSE_ERR_ARG;
+  if (reduce != CMHSE_GROUP_MAX && reduce != CMHSE_GROUP_MEAN) return CMHSE_ERR_ARG;
+  if (!gt_plan_ok(plan_host, plan_len_, Nc, Ns, direction, K)) return CMHSE_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
+      workspace_bytes < cmhse_group_topk_workspace(plan_host, plan_len_))
+    return CMHSE_ERR_WORKSPACE;
+  const int32_t Bv = plan_host[0], Bp = plan_host[1], R = plan_host[6], Cc = plan_host[7];
+  GroupTopkParams p;
+  p.C = clips;
+  p.S = caps;
+  p.D = D;
+  p.use_max = reduce == CMHSE_GROUP_MAX;
+  p.p2v = direction == CMHSE_GROUP_P2V;
+  p.K = K;
+  p.Bq = p.p2v ? Bp : Bv;
+  p.q_tiles = p.p2v ? Cc : R;
+  p.g_tiles = p.p2v ? R : Cc;
+  p.panels = gt_panels(p.q_tiles, p.g_tiles, K);
+  p.clip_off = plan + kGtHdr;
+  p.cap_off = p.clip_off + Bv + 1;
+  p.rt_vid = p.cap_off + Bp + 1;
+  p.ct_par = p.rt_vid + R + 1;
+  p.ws = static_cast<score_key_t*>(workspace);
+  const int64_t blocks = (static_cast<int64_t>(p.q_tiles) * p.panels + 7) / 8 * 8;
+  if (blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int rc = launch_tiles(group_topk_select_kernel<true>, group_topk_select_kernel<false>, D,
+                              dim3(static_cast<unsigned>(blocks)), gt_smem(K), stream, p);
+  if (rc != CMHSE_OK) return rc;
+  const PanelLists lists = {p.ws, p.panels, p.Bq, K, scores, index};
+  hipLaunchKernelGGL(group_topk_merge_kernel, dim3((p.Bq + 3) / 4), dim3(kThreads), 0, stream, lists);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }

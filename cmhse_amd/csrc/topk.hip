@@ -15,7 +15,8 @@
 //                       row's current K-th key picks the candidates (few once the list is warm: about
 //                       K (1 + ln(M / K)) per row over a random-order gallery), which are merged into
 //                       the row's sorted list in LDS.  The panel's K keys per row go to the workspace.
-//   topk_merge_kernel   one wave per row merges the P panel lists the same way and decodes the keys.
+//   topk_merge_kernel   one wave per row merges the P panel lists the same way and decodes the keys
+//                       (wave_merge and merge_panel_lists: topk_lists.hpp, shared with group.hip).
 // 64-row tiles rather than sim_rank's 128: the running lists live in LDS, 64 rows x K x 8 B (64 KB at
 // K = 128); 128 rows would need 128 KB beside the tile buffers, more than a CU has for one workgroup
 // at K = 128, and half of that already leaves one workgroup per CU at K = 50.
@@ -25,6 +26,7 @@
 #include "../../include/cmhse_hip.h"
 #include "nt_core.hpp"
 #include "score_tile.hpp"
+#include "topk_lists.hpp"
 
 namespace cmhse {
 namespace {
@@ -46,53 +48,7 @@ struct TopkParams {
   int32_t M, D, row0, nrows, K;
   int32_t row_tiles, col_tiles, panels;
   score_key_t* ws;   // [panels, nrows, K] sorted keys of each panel
-  float* scores;     // [nrows, K]
-  int32_t* index;    // [nrows, K]
 };
-
-// One wave merges c candidate keys (cand[0, c), unsorted, c <= 128, all above lst[K - 1]) into the
-// descending list lst[0, K) (0 = empty slot; a real key is never 0).  Keys are unique, so each one's
-// place in the merged order is its rank: a list entry moves down by the candidates above it, a
-// candidate lands at (list entries above it) + (candidates above it); what lands past K drops out.
-// Every lane has read all it needs before any lane writes (lock-step wave, in-order LDS).
-__device__ __forceinline__ void wave_merge(score_key_t* lst, int K, const score_key_t* cand, int c, int lane) {
-  score_key_t lv[2], cv[2];
-  int lr[2] = {0, 0}, cr[2] = {0, 0};
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int e = lane + 64 * h;
-    lv[h] = e < K ? lst[e] : 0ull;
-    cv[h] = e < c ? cand[e] : 0ull;
-  }
-  for (int q = 0; q < c; ++q) {
-    const score_key_t x = cand[q];   // (one address for the whole wave: a broadcast read)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      lr[h] += x > lv[h];
-      cr[h] += x > cv[h];
-    }
-  }
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    if (lane + 64 * h < c) {
-      int lo = 0, hi = K;       // list entries above the candidate (descending, empty slots last)
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (lst[mid] > cv[h]) lo = mid + 1;
-        else hi = mid;
-      }
-      cr[h] += lo;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int e = lane + 64 * h;
-    if (e < K && e + lr[h] < K) lst[e + lr[h]] = lv[h];
-    if (e < c && cr[h] < K) lst[cr[h]] = cv[h];
-  }
-  __builtin_amdgcn_wave_barrier();
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void topk_select_kernel(const TopkParams p) {
@@ -162,35 +118,13 @@ __global__ __launch_bounds__(kThreads) void topk_select_kernel(const TopkParams 
 }
 
 // One wave per row: the P panel lists (each sorted: its candidates are a prefix) into one, decoded.
-__global__ __launch_bounds__(kThreads) void topk_merge_kernel(const TopkParams p) {
+__global__ __launch_bounds__(kThreads) void topk_merge_kernel(const PanelLists p) {
   __shared__ score_key_t s_list[kThreads / 64][CMHSE_TOPK_MAX];
   __shared__ score_key_t s_cand[kThreads / 64][CMHSE_TOPK_MAX];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = blockIdx.x * (kThreads / 64) + wave;
   if (li >= p.nrows) return;   // (no barrier below)
-  const int K = p.K;
-  score_key_t* lst = s_list[wave];
-  score_key_t* cand = s_cand[wave];
-  for (int e = lane; e < K; e += 64) lst[e] = 0ull;
-  __builtin_amdgcn_wave_barrier();
-  for (int q = 0; q < p.panels; ++q) {
-    const score_key_t* src = p.ws + (static_cast<int64_t>(q) * p.nrows + li) * K;
-    const score_key_t thr = lst[K - 1];
-    const score_key_t k0 = lane < K ? src[lane] : 0ull;
-    const score_key_t k1 = lane + 64 < K ? src[lane + 64] : 0ull;
-    const bool c0 = k0 > thr, c1 = k1 > thr;
-    const int c = __popcll(__ballot(c0)) + __popcll(__ballot(c1));
-    if (c == 0) continue;
-    if (c0) cand[lane] = k0;
-    if (c1) cand[lane + 64] = k1;
-    __builtin_amdgcn_wave_barrier();
-    wave_merge(lst, K, cand, c, lane);
-  }
-  for (int e = lane; e < K; e += 64) {
-    const score_key_t key = lst[e];
-    p.scores[static_cast<int64_t>(li) * K + e] = key_score(key);
-    p.index[static_cast<int64_t>(li) * K + e] = key_index(key);
-  }
+  merge_panel_lists(p, li, s_list[wave], s_cand[wave], lane);
 }
 
 size_t topk_smem(int K) {
@@ -245,14 +179,13 @@ extern "C" int cmhse_sim_topk(const float* A, const float* B, int32_t N, int32_t
   p.col_tiles = (M + kTkBN - 1) / kTkBN;
   p.panels = topk_panels(nrows, M, K);
   p.ws = static_cast<score_key_t*>(workspace);
-  p.scores = scores;
-  p.index = index;
   const int64_t blocks = (static_cast<int64_t>(p.row_tiles) * p.panels + 7) / 8 * 8;
   if (blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
   // (past 64 KiB of LDS for K > 52)
   const int rc = launch_tiles(topk_select_kernel<true>, topk_select_kernel<false>, D,
                               dim3(static_cast<unsigned>(blocks)), topk_smem(K), stream, p);
   if (rc != CMHSE_OK) return rc;
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((nrows + 3) / 4), dim3(kThreads), 0, stream, p);
+  const PanelLists lists = {p.ws, p.panels, nrows, K, scores, index};
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((nrows + 3) / 4), dim3(kThreads), 0, stream, lists);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }

@@ -879,6 +879,40 @@ def group_i2t_t2i(clip_embs, cap_embs, num_clips, num_caps=None, reduce='max'):
           (report_from_ranks(host[2]), host[3], host[2]))
 
 
+def group_retrieve(clip_embs, cap_embs, num_clips, num_caps=None, k=10, direction='p2v', reduce='max'):
+  """Top-k retrieval by the group-wise score of the low level (group_i2t_t2i's score: block max of
+  the clip x caption scores of a (video, paragraph) pair with max_violation, block mean without):
+  direction 'p2v' gives the k best videos for every paragraph, 'v2p' the k best paragraphs for every
+  video, best first, smaller index first on exact ties (ops.group_topk: matrix-free, exact fp32).
+  The video set (clip rows, num_clips) and the paragraph set (caption rows, num_caps) may differ in
+  size — a new set of query paragraphs against a video gallery:
+
+    vid, para, clip, cap, _, _, nclips, _ = encode_data(opt, model, loader)
+    scores, index = group_retrieve(clip, cap, nclips, k=10, direction='p2v',
+                                   reduce='max' if opt.max_violation else 'mean')
+
+  NumPy in, NumPy out: scores float32 [Bq, k] and index int64 [Bq, k].  GPU tensors in: device
+  tensors out (float32, int32), on the current stream.  num_caps defaults to num_clips.  The ranking
+  cache i2t / t2i serve from is neither read nor changed."""
+  num_caps = num_clips if num_caps is None else num_caps
+  if reduce not in ('max', 'mean'):
+    raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
+  for x, name in ((clip_embs, 'clip_embs'), (cap_embs, 'cap_embs')):
+    if len(getattr(x, 'shape', ())) != 2:
+      raise ValueError('%s must be 2-D' % name)
+  if clip_embs.shape[1] != cap_embs.shape[1]:
+    raise ValueError('embedding widths differ')
+  # argument errors before the upload
+  ops.group_topk_plan(num_clips, num_caps, len(clip_embs), len(cap_embs), k, direction)
+  on_device = isinstance(clip_embs, torch.Tensor) and clip_embs.is_cuda
+  c = _as_device(clip_embs)
+  s = _as_device(cap_embs, c.device)
+  scores, index = ops.group_topk(c, s, num_clips, num_caps, k, direction, reduce)
+  if on_device:
+    return scores, index
+  return scores.cpu().numpy(), index.cpu().numpy().astype(numpy.int64)
+
+
 def _rank_report(queries, gallery):
   rank, top1 = ops.sim_rank(_as_device(queries), _as_device(gallery))
   ranks = rank.cpu().numpy().astype(numpy.float64)      # the reference stores ranks in float64

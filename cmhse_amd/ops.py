@@ -908,6 +908,76 @@ def group_rank(clips, caps, num_clips, num_caps=None, reduce='max'):
   return out[0], out[1], out[2], out[3]
 
 
+_GROUP_DIRECTION = {'p2v': _lib.GROUP_P2V, 'v2p': _lib.GROUP_V2P}
+
+
+def group_topk_plan(num_clips, num_caps, n_clip_rows, n_cap_rows, k, direction='p2v'):
+  """The host plan of cmhse_group_topk_plan (int32 NumPy) for any video set (num_clips) and any
+  paragraph set (num_caps); ValueError on a bad direction, a k outside [1, min(gallery groups, 128)],
+  counts that do not tile the rows or a video / paragraph longer than 128 rows.  No GPU."""
+  if direction not in _GROUP_DIRECTION:
+    raise ValueError("direction must be 'p2v' or 'v2p', got %r" % (direction,))
+  nclips = _group_counts(num_clips, 'num_clips')
+  ncaps = _group_counts(num_caps, 'num_caps')
+  if int(nclips.sum()) != n_clip_rows or int(ncaps.sum()) != n_cap_rows:
+    raise ValueError('the counts must tile the rows: sum(num_clips) = %d for %d clip rows, '
+                     'sum(num_caps) = %d for %d caption rows'
+                     % (nclips.sum(), n_clip_rows, ncaps.sum(), n_cap_rows))
+  longest = max(int(nclips.max()), int(ncaps.max()))
+  if longest > _lib.GROUP_TILE_ROWS:
+    raise ValueError('a video or paragraph of %d rows: group scores support at most %d'
+                     % (longest, _lib.GROUP_TILE_ROWS))
+  gallery = nclips.size if direction == 'p2v' else ncaps.size
+  if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= min(gallery, _lib.TOPK_MAX):
+    raise ValueError('k must be an integer in [1, min(gallery groups = %d, %d)], got %r'
+                     % (gallery, _lib.TOPK_MAX, k))
+  Bv, Bp = nclips.size, ncaps.size
+  oc = np.zeros(Bv + 1, dtype=np.int32)
+  op = np.zeros(Bp + 1, dtype=np.int32)
+  np.cumsum(nclips, out=oc[1:])
+  np.cumsum(ncaps, out=op[1:])
+  plan = np.empty(_lib.group_topk_plan_max(Bv, Bp), dtype=np.int32)
+  n = _lib.load().cmhse_group_topk_plan(oc.ctypes.data, Bv, op.ctypes.data, Bp, _GROUP_DIRECTION[direction],
+                                        int(k), plan.ctypes.data, plan.size)
+  _lib.check(min(n, 0), 'cmhse_group_topk_plan')
+  return plan[:n]
+
+
+def group_topk(clips, caps, num_clips, num_caps, k, direction='p2v', reduce='max'):
+  """The k best gallery groups of every query group by group_scores' block score
+  (cmhse_group_topk): direction 'p2v' takes every paragraph of caps / num_caps as a query against
+  the videos of clips / num_clips, 'v2p' the reverse; the two sets are independent (any number of
+  videos and paragraphs).  Returns (scores float32 [Bq, k], index int32 [Bq, k]) device tensors on
+  the current stream: score descending, smaller gallery index first on exact ties, the scores
+  bit-identical to the block reduction of group_scores ('max' / 'mean').  Exact fp32 whatever
+  math_mode() says; neither the clip x caption nor the query x gallery matrix is stored."""
+  if reduce not in _GROUP_REDUCE:
+    raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
+  if direction not in _GROUP_DIRECTION:
+    raise ValueError("direction must be 'p2v' or 'v2p', got %r" % (direction,))
+  for t, name in ((clips, 'clips'), (caps, 'caps')):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+      raise ValueError('%s must be a 2-D tensor' % name)
+  if clips.shape[1] != caps.shape[1]:
+    raise ValueError('embedding widths differ')
+  plan = group_topk_plan(num_clips, num_caps, clips.shape[0], caps.shape[0], k, direction)
+  lib = _lib.load()
+  c = _f32c(clips, 'clips')
+  s = _f32c(caps, 'caps')
+  k = int(k)
+  Bq = int(plan[1] if direction == 'p2v' else plan[0])
+  scores = torch.empty(Bq, k, dtype=torch.float32, device=c.device)
+  index = torch.empty(Bq, k, dtype=torch.int32, device=c.device)
+  ws_bytes = lib.cmhse_group_topk_workspace(plan.ctypes.data, plan.size)
+  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=c.device)
+  plan_d = upload(plan, c.device)
+  rc = lib.cmhse_group_topk(c.data_ptr(), s.data_ptr(), c.shape[0], s.shape[0], c.shape[1], plan.ctypes.data,
+                            plan_d.data_ptr(), plan.size, _GROUP_DIRECTION[direction], _GROUP_REDUCE[reduce], k,
+                            scores.data_ptr(), index.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+  _lib.check(rc, 'cmhse_group_topk')
+  return scores, index
+
+
 def cosine_sim(im, s):
   """loss.cosine_sim on device: im @ s.T, exact fp32 (cmhse_cosine_sim)."""
   lib = _lib.load()

@@ -353,6 +353,50 @@ int cmhse_group_rank(const float* clips, const float* caps, int32_t Nc, int32_t 
                      int32_t reduce, int32_t* rank_v2p, int32_t* top1_v2p, int32_t* rank_p2v,
                      int32_t* top1_p2v, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Group-wise top-K retrieval: the K best gallery groups of every query group by the block score
+ * above, for any video set and any paragraph set (Bv videos of clips, Bp paragraphs of caps: Bv and
+ * Bp independent, every count 1..CMHSE_GROUP_TILE_ROWS rows).
+ *   CMHSE_GROUP_P2V  every paragraph j is a query, the videos are the gallery: [Bp, K] results;
+ *   CMHSE_GROUP_V2P  every video i is a query, the paragraphs are the gallery: [Bv, K] results.
+ *   scores[q, :]  the block scores, bit-identical to the reduction cmhse_group_scores computes (in
+ *                 the square case the same entries of its G, in both reduce modes: the mean stays
+ *                 clip-major, then caption, with the fp64 sum, whichever side is the query);
+ *   index[q, :]   their gallery groups, by score descending, then by index ascending on exact ties
+ *                 (the 64-bit key of cmhse_sim_topk, unique per query: the result depends on neither
+ *                 tiling nor scheduling, and K == gallery size is a full stable sort).
+ * 1 <= K <= min(gallery groups, CMHSE_TOPK_MAX).  Exact fp32 whatever the math mode.  Neither the
+ * Nc x Ns clip x caption matrix nor the Bq x Bg matrix of block scores is stored: each workgroup holds
+ * one query tile and walks a panel of gallery tiles, reducing each tile's blocks in LDS and merging
+ * them into per-query sorted lists; a second pass merges the panels' lists.  The panel count fills
+ * the CUs once, so the workspace (panels x Bq x K keys) is fixed by the query side and K, not by the
+ * gallery (once the gallery has as many tiles as there are panels).  A query subset is a smaller call
+ * with its rows and counts sliced: the results of query stripes concatenate bit for bit into the
+ * whole call's.
+ *
+ * cmhse_group_topk_plan (host only, no GPU needed): from the host prefix sums clip_off_host[Bv+1] and
+ * cap_off_host[Bp+1] (0 first, strictly increasing) fills plan[0, len) and returns len, or
+ * CMHSE_ERR_ARG (null pointer, Bv or Bp <= 0, bad prefix sums, bad direction, K outside
+ * [1, min(gallery groups, CMHSE_TOPK_MAX)]), CMHSE_ERR_UNSUPPORTED (a video or paragraph of more than
+ * 128 rows), CMHSE_ERR_WORKSPACE (plan_cap < CMHSE_GROUP_TOPK_PLAN_MAX(Bv, Bp)).  Layout (int32):
+ * Bv, Bp, Nc, Ns, direction, K, R clip tiles, C caption tiles, clip_off[Bv+1], cap_off[Bp+1], the
+ * first video of each clip tile [R+1], the first paragraph of each caption tile [C+1].  The gallery
+ * side packs as cmhse_group_plan does (whole groups, <= 128 rows a tile); the query side also caps
+ * the groups of a tile at a number derived from K (the LDS its lists take).  As for cmhse_group_scores
+ * the caller uploads plan[0, len) and passes both copies; direction and K are recorded in the plan and
+ * must equal the call's.
+ * cmhse_group_topk_workspace: bytes for the plan (0 for an invalid plan), 256-byte aligned.
+ * Argument errors are returned before anything is launched. */
+#define CMHSE_GROUP_P2V 0
+#define CMHSE_GROUP_V2P 1
+#define CMHSE_GROUP_TOPK_PLAN_MAX(Bv, Bp) (2 * (Bv) + 2 * (Bp) + 12)
+int32_t cmhse_group_topk_plan(const int32_t* clip_off_host, int32_t Bv, const int32_t* cap_off_host,
+                              int32_t Bp, int32_t direction, int32_t K, int32_t* plan, int32_t plan_cap);
+size_t cmhse_group_topk_workspace(const int32_t* plan_host, int32_t plan_len);
+int cmhse_group_topk(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                     const int32_t* plan_host, const int32_t* plan, int32_t plan_len, int32_t direction,
+                     int32_t reduce, int32_t K, float* scores /*[Bq,K]*/, int32_t* index /*[Bq,K]*/,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* Replaces loss.cosine_sim (loss.py:12-13): scores[n,m] = im s^T, exact fp32. */
 int cmhse_cosine_sim(const float* im, const float* s, int32_t n, int32_t m, int32_t D,
                      float* scores, void* stream);
