@@ -38,7 +38,9 @@ class SeqBatch(ctypes.Structure):
               ('vocab', c_int32), ('h0_rows', c_void_p), ('lens', c_void_p),
               ('out_row', c_void_p), ('step_off', c_void_p), ('step_count_host', c_void_p),
               ('step_timer', c_void_p), ('step_events_host', c_void_p),
-              ('step_plan_host', c_void_p)]
+              ('step_plan_host', c_void_p),
+              ('n_alias', c_int32), ('alias_src', c_void_p), ('alias_len', c_void_p),
+              ('alias_out_row', c_void_p), ('alias_src_host', c_void_p), ('alias_len_host', c_void_p)]
 
 
 class GruJob(ctypes.Structure):
@@ -97,6 +99,8 @@ SIGNATURES = {
                                         c_int32, c_void_p]),
     'cmhse_push_rows': (ctypes.c_int, [c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_void_p]),
     'cmhse_rows_differ': (ctypes.c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'cmhse_tok_prefix_check': (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
     'cmhse_pad_rows': (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                       c_void_p, c_void_p]),
     'cmhse_l2norm_rows': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),

@@ -312,6 +312,18 @@ int prepare_job(const cmhse_seq_batch* b, const cmhse_gru_weights* w, int32_t po
     for (int t = 0; t < b->Tmax; ++t)
       if (b->step_plan_host[t] < b->step_count_host[t] || (t > 0 && b->step_plan_host[t] > b->step_plan_host[t - 1]))
         return CMHSE_ERR_ARG;
+  if (b->n_alias < 0) return CMHSE_ERR_ARG;
+  if (b->n_alias > 0) {
+    // prefix aliases: attention-pooled inference requests only; every alias inside its source sequence
+    // (sorted sequence s has #{t : step_count_host[t] > s} steps)
+    if (pool_mode != CMHSE_POOL_ATTN || save) return CMHSE_ERR_ARG;
+    if (!b->alias_src || !b->alias_len || !b->alias_out_row || !b->alias_src_host || !b->alias_len_host)
+      return CMHSE_ERR_ARG;
+    for (int i = 0; i < b->n_alias; ++i) {
+      const int32_t s = b->alias_src_host[i], len = b->alias_len_host[i];
+      if (s < 0 || s >= b->S || len < 1 || len > b->Tmax || b->step_count_host[len - 1] <= s) return CMHSE_ERR_ARG;
+    }
+  }
   if (sum_T * b->H >= (int64_t(1) << 40)) return CMHSE_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
       workspace_bytes < cmhse_gru_pool_workspace(b->S, b->Tmax, sum_T, b->I, b->H, mode_flags))
@@ -1200,11 +1212,17 @@ int launch_attention(FwdJob& job, hipStream_t stream, int64_t row_end, bool pool
   pp.lens = b->lens;
   pp.out_row = b->out_row;
   pp.step_off = b->step_off;
+  pp.alias_src = b->alias_src;
+  pp.alias_len = b->alias_len;
+  pp.alias_out_row = b->alias_out_row;
   pp.out = job.out;
   pp.rows = sum_T;
   pp.H = b->H;
   pp.n_tiles = att_tiles;
-  hipLaunchKernelGGL(attn_pool_kernel, dim3(b->S), dim3(kThreads), 0, stream, pp);
+  pp.S = b->S;
+  // one workgroup per sequence, then one per prefix alias (validated in prepare_job)
+  hipLaunchKernelGGL(attn_pool_kernel, dim3(static_cast<unsigned>(b->S) + static_cast<unsigned>(b->n_alias)),
+                     dim3(kThreads), 0, stream, pp);
   return CMHSE_OK;
 }
 
@@ -1371,6 +1389,17 @@ extern "C" int cmhse_rows_differ(const void* a, const void* b, size_t bytes, int
                      static_cast<const uint4*>(a), static_cast<const uint4*>(b), n16,
                      static_cast<const unsigned char*>(a) + (n16 << 4),
                      static_cast<const unsigned char*>(b) + (n16 << 4), tail, flag);
+  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
+}
+
+extern "C" int cmhse_tok_prefix_check(int32_t n, const uint64_t* a_rows, const uint64_t* b_rows,
+                                      const int32_t* a_len, const int32_t* b_len, int32_t* flags,
+                                      void* stream_) {
+  if (n < 0) return CMHSE_ERR_ARG;
+  if (n == 0) return CMHSE_OK;
+  if (!a_rows || !b_rows || !a_len || !b_len || !flags) return CMHSE_ERR_ARG;
+  hipLaunchKernelGGL(tok_prefix_kernel, dim3(static_cast<unsigned>(n)), dim3(64), 0,
+                     static_cast<hipStream_t>(stream_), a_rows, b_rows, a_len, b_len, flags, n);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }
 

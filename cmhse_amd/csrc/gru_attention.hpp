@@ -115,7 +115,9 @@ void attn_energy_kernel(const AttnEnergyParams p) {
 
 // ---------------------------------------------------------------------------------------------
 // attention pooling: out[s] = sum_t a_t h_t,  a_t = exp(e_t) [t < len] / (sum_t exp(e_t) + 1e-4)
-// one workgroup per sequence; reads each hidden row once (HBM-bound).
+// one workgroup per sequence; reads each hidden row once (HBM-bound).  Workgroups [S, S + n_alias) are
+// prefix aliases (cmhse_seq_batch.n_alias): the first alias_len steps of sequence alias_src through the
+// same body — denominator and weighted sum in the order a real sequence of that length gets.
 // ---------------------------------------------------------------------------------------------
 struct AttnPoolParams {
   const float* hs;
@@ -123,14 +125,20 @@ struct AttnPoolParams {
   const int32_t* lens;
   const int32_t* out_row;
   const int32_t* step_off;
+  const int32_t* alias_src;
+  const int32_t* alias_len;
+  const int32_t* alias_out_row;
   float* out;
   int64_t rows;
-  int32_t H, n_tiles;
+  int32_t H, n_tiles, S;
 };
 
 __global__ __launch_bounds__(kThreads) void attn_pool_kernel(const AttnPoolParams p) {
-  const int s = blockIdx.x;
-  const int len = p.lens[s];
+  const int alias = static_cast<int>(blockIdx.x) - p.S;
+  const int s = alias >= 0 ? p.alias_src[alias] : static_cast<int>(blockIdx.x);
+  int len = p.lens[s];
+  if (alias >= 0 && p.alias_len[alias] < len) len = p.alias_len[alias];   // (never beyond the source's rows)
+  const int orow = alias >= 0 ? p.alias_out_row[alias] : p.out_row[s];
   const int tid = threadIdx.x;
   __shared__ float s_w[kThreads];
   __shared__ int64_t s_row[kThreads];
@@ -153,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void attn_pool_kernel(const AttnPoolParam
   __syncthreads();
   const float den = s_den;
   const int H = p.H;
-  float* o = p.out + static_cast<int64_t>(p.out_row[s]) * H;
+  float* o = p.out + static_cast<int64_t>(orow) * H;
   const bool vec = (H % 4 == 0) && aligned16(p.hs) && aligned16(o);
   // pass 2: weighted sum over the sequence's rows; the weights AND the packed row numbers of 256
   // steps at a time are staged in LDS, so the row loads of consecutive steps are independent of any

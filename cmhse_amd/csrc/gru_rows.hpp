@@ -174,6 +174,28 @@ __global__ __launch_bounds__(64) void rows_differ_kernel(const uint4* __restrict
   if (__builtin_amdgcn_ballot_w64(diff != 0) != 0 && threadIdx.x == 0) atomicOr(flag, 1);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Is token sequence a_rows[i] (a_len[i] int64 ids) a prefix of b_rows[i] (b_len[i] ids)?  One wave per
+// pair (a validation pass asks for 4917 pairs, 75 k ids); flags[i] = 1 / 0.  cmhse_tok_prefix_check.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void tok_prefix_kernel(const uint64_t* __restrict__ a_rows,
+                                                       const uint64_t* __restrict__ b_rows,
+                                                       const int32_t* __restrict__ a_len,
+                                                       const int32_t* __restrict__ b_len,
+                                                       int32_t* __restrict__ flags, int n) {
+  const int i = blockIdx.x;
+  if (i >= n) return;
+  const int la = a_len[i], lb = b_len[i];
+  bool diff = la < 0 || lb < la;      // (wave-uniform)
+  if (!diff) {
+    const long long* a = reinterpret_cast<const long long*>(a_rows[i]);
+    const long long* b = reinterpret_cast<const long long*>(b_rows[i]);
+    for (int t = threadIdx.x; t < la; t += 64) diff |= a[t] != b[t];
+  }
+  const bool any = __builtin_amdgcn_ballot_w64(diff) != 0;
+  if (threadIdx.x == 0) flags[i] = any ? 0 : 1;
+}
+
 // bf16x3 pre-split of a weight matrix W [R, K] (fp32, row stride K): row r of `out` has
 // split_ld(K) float units; per 16-k chunk 8 dwords of hi pairs then 8 dwords of lo pairs
 // (k beyond K zero-filled), see nt_phase_bf3.

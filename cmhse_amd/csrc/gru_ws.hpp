@@ -70,7 +70,8 @@ struct GruWs {
   X(early_xproj, 1)           /* 1: an inference call's hoisted projection starts on the side stream before the first step */ \
   X(chain_tall_min_wgs, 256)  /* 64-row workgroups per step from which a step chain uses 128-row tiles */ \
   X(pull_waves, 32)           /* single-wave workgroups of one cmhse_pull_steps launch (host -> HBM over PCIe) */ \
-  X(tok_table, 1)             /* 1: a token-fed exact inference call with word-steps >= 4 x vocab projects the vocabulary once */
+  X(tok_table, 1)             /* 1: a token-fed exact inference call with word-steps >= 4 x vocab projects the vocabulary once */ \
+  X(share_prefix, 1)          /* 1: the host glue pools a video's first caption from its paragraph's rows (cmhse_seq_batch.n_alias) */
 
 struct Tunables {
 #define CMHSE_TUNABLE_MEMBER_(name, dflt) std::atomic<int> name{dflt};

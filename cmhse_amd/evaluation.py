@@ -17,8 +17,10 @@ from __future__ import annotations
 import contextlib
 import gc
 import hashlib
+import itertools
 import os
 import time
+import collections
 from collections import OrderedDict
 
 import numpy
@@ -235,8 +237,12 @@ def _plan_key(group):
   in-place edit of any batch's lengths, a swapped or re-uploaded batch anywhere in the list, or a
   different number of batches gives a different key, and encode_group rebuilds the plan
   (tests/test_gpu_pipeline.py::test_plan_key_*).  What the key cannot see is an in-place edit of the
-  feature VALUES — those are read afresh on every pass anyway (a plan holds addresses and
-  schedules, not data).  A plan keeps its group's device tensors alive (`keep`): the whole resident
+  VALUES.  Feature values are read afresh on every pass anyway (a plan holds addresses and schedules),
+  with ONE exception since the prefix sharing (tunable share_prefix): the plan also keeps which first
+  captions were token-for-token prefixes of their paragraphs when it was built, a fact derived from
+  the token values.  Token ids edited in place under a kept plan would leave the edited captions'
+  `cap_emb` rows pooled from their paragraphs: drop the plan (or clear the dict) after such an edit.
+  A plan keeps its group's device tensors alive (`keep`): the whole resident
   split, 14.7 GB for ActivityNet-ICEP val; drop the plan dict to release them."""
   h = hashlib.blake2b(digest_size=16)
   ptrs = np.empty(4 * len(group), dtype=np.uint64)
@@ -290,7 +296,157 @@ def split_step_plan(batches):
   return plan_from_histograms(length_histograms(batches))
 
 
-def encode_group(model, group, contextual_model=True, device=None, plan=None, step_plan=None, stage=None):
+# Prefix sharing of the text tower (tunable "share_prefix", include/cmhse_hip.h).  A paragraph is the
+# concatenation of its captions (activity_net/data.py:78) and both run through txt_enc from h0 = 0 in one
+# request, so the hidden states and attention energies of a video's FIRST caption are those of its
+# paragraph's first len(caption) steps, bit for bit.  Where the tokens say so (checked on the data of
+# every call, text_prefix_flags) the caption is left out of the level-1 text request and its embedding is
+# pooled from the paragraph's rows (cmhse_seq_batch.n_alias).  Attention pooling only: max and last
+# pooling are fused into the step epilogue and would need a second epilogue target (a possible follow-up).
+# Write-only for the library (tests and tools read it): the first captions the last encode_data_device
+# call pooled from their paragraphs, of how many captions.  encode_group reports its own in its result.
+SHARE_STATS = {'aliases': 0, 'captions': 0}
+
+# What the token check of one group hands to encode_group: the flags and, for a group of resident padded
+# batches, the level-1 text tables the check had to build anyway (captions then paragraphs), else None.
+PrefixCheck = collections.namedtuple('PrefixCheck', 'flags t_lens t_ptrs num_caps')
+
+
+def text_prefix_aliases(len_cap, len_par, num_caps, ok_flags=None):
+  """The planner of the prefix sharing, pure NumPy.  len_cap [n_cap] caption lengths in loader order
+  (video after video), len_par [n_vid] paragraph lengths, num_caps [n_vid] captions per video (>= 1),
+  ok_flags [n_vid] (optional): nonzero where the first caption's tokens ARE the paragraph's first
+  tokens.  Returns (kept, (vid, length, cap_row)): the caption indices that stay in the request, and per
+  alias the video whose paragraph is the source, the caption's length and its row of cap_emb.  A video
+  is aliased only if its flag is set and its paragraph is at least as long as its first caption; a
+  single-caption video aliases its whole paragraph."""
+  len_cap = np.asarray(len_cap, dtype=np.int64).reshape(-1)
+  len_par = np.asarray(len_par, dtype=np.int64).reshape(-1)
+  num_caps = np.asarray(num_caps, dtype=np.int64).reshape(-1)
+  if len(num_caps) != len(len_par) or int(num_caps.sum()) != len(len_cap) or (num_caps < 1).any():
+    raise ValueError('text_prefix_aliases: one paragraph and at least one caption per video')
+  first = np.cumsum(num_caps) - num_caps
+  l0 = len_cap[first]
+  ok = len_par >= l0
+  if ok_flags is not None:
+    ok &= np.asarray(ok_flags).reshape(-1) != 0
+  keep = np.ones(len(len_cap), dtype=bool)
+  keep[first[ok]] = False
+  vid = np.flatnonzero(ok)
+  return np.flatnonzero(keep), (vid, l0[vid], first[vid])
+
+
+def _share_on(model):
+  """Does encode_group share first captions for this model under the current settings?"""
+  rnn = model.txt_enc.rnn
+  return (GROUP_TOWERS[0] and not TWO_STREAMS[0] and rnn.POOL == ops.POOL_ATTN and
+          not getattr(rnn.rnn, 'bidirectional', False) and ops.tune('share_prefix') != 0)
+
+
+def _resident_tokens(t, device):
+  """A token tensor the encoders read in place (what _dev_seq hands back unchanged)."""
+  d = t.data if isinstance(t, ops.Ragged) else t
+  return (isinstance(d, torch.Tensor) and d.is_cuda and d.dtype == torch.int64 and d.is_contiguous() and
+          d.device == device)
+
+
+def _host_prefix_flags(caps, pars, first, l0, len_par):
+  """text_prefix_flags for one batch whose token tensors are in host memory."""
+  ok = len_par >= l0
+  if isinstance(caps, ops.Ragged) or isinstance(pars, ops.Ragged) or caps.dim() != 2 or pars.dim() != 2:
+    rows_c = (lambda i: caps.data[caps.first[i]:caps.first[i] + caps.lens[i]]) if isinstance(caps, ops.Ragged) \
+        else (lambda i: caps[i])
+    rows_p = (lambda i: pars.data[pars.first[i]:pars.first[i] + pars.lens[i]]) if isinstance(pars, ops.Ragged) \
+        else (lambda i: pars[i])
+    for v in np.flatnonzero(ok):
+      n = int(l0[v])
+      a, b = rows_c(int(first[v]))[:n], rows_p(int(v))[:n]
+      ok[v] = a.shape[0] == n and b.shape[0] == n and bool(torch.equal(a.long(), b.long()))
+    return ok
+  a, b = caps.numpy()[first], pars.numpy()
+  w = min(a.shape[1], b.shape[1])
+  ok &= l0 <= w
+  inside = np.arange(w, dtype=np.int64)[None, :] < l0[:, None]
+  return ok & ((a[:, :w] == b[:, :w]) | ~inside).all(axis=1)
+
+
+def text_prefix_flags(groups, device):
+  """The flags of _prefix_checks alone."""
+  return [c.flags for c in _prefix_checks(groups, device)]
+
+
+def _prefix_checks(groups, device):
+  """For every group (list of loader batches) a bool array [videos of the group]: True where the tokens
+  of the video's first caption are the first tokens of its paragraph (raw ids).  Token tensors that
+  are resident on `device` are compared there by one cmhse_tok_prefix_check launch over ALL groups and
+  one read-back (the only host synchronisation of the sharing; it stands in front of every launch of
+  the pass); token tensors in host memory are compared on the host.  Anything else: False.
+  Returns one PrefixCheck per group; for a group of resident padded batches it carries the level-1 text
+  tables (t_lens, t_ptrs, num_caps), which encode_group takes over instead of building them again."""
+  out, parts, tables = [], [], []
+  for gi, group in enumerate(groups):
+    if all(type(b[1]) is torch.Tensor and type(b[3]) is torch.Tensor and _resident_tokens(b[1], device) and
+           _resident_tokens(b[3], device) for b in group):
+      # a resident split of padded batches (bench.py, a validation set kept in HBM): one pass of NumPy
+      # over the whole group instead of a few small arrays per loader batch
+      nc = np.fromiter(itertools.chain.from_iterable(b[9] for b in group), dtype=np.int64)
+      first = np.cumsum(nc) - nc
+      t_ptrs = ops.seq_row_ptrs_many([b[1] for b in group] + [b[3] for b in group])
+      t_lens = np.concatenate([_lens_i64(b[5]) for b in group] + [_lens_i64(b[7]) for b in group])
+      n_cap = len(t_lens) - len(nc)
+      parts.append((gi, 0, t_ptrs[first], t_ptrs[n_cap:], t_lens[first], t_lens[n_cap:]))
+      out.append(np.zeros(len(nc), dtype=bool))
+      tables.append((t_lens, t_ptrs, nc))
+      continue
+    tables.append((None, None, None))
+    flags = np.zeros(sum(len(b[9]) for b in group), dtype=bool)
+    off = 0
+    for b in group:
+      nc = np.asarray(b[9], dtype=np.int64)
+      first = np.cumsum(nc) - nc
+      l0, lp = _lens_i64(b[5])[first], _lens_i64(b[7])
+      caps, pars = b[1], b[3]
+      if _resident_tokens(caps, device) and _resident_tokens(pars, device):
+        parts.append((gi, off, ops.seq_row_ptrs(caps)[first], ops.seq_row_ptrs(pars), l0, lp))
+      elif not caps.is_cuda and not pars.is_cuda:
+        flags[off:off + len(nc)] = _host_prefix_flags(caps, pars, first, l0, lp)
+      off += len(nc)
+    out.append(flags)
+  if parts:
+    cols = [p[2:] for p in parts]
+    cols = cols[0] if len(cols) == 1 else [np.concatenate([c[k] for c in cols]) for k in range(4)]
+    host = ops.tok_prefix_check(*cols, device).cpu().numpy() != 0
+    at = 0
+    for gi, off, a, _, _, _ in parts:
+      out[gi][off:off + len(a)] = host[at:at + len(a)]
+      at += len(a)
+  return [PrefixCheck(f, *t) for f, t in zip(out, tables)]
+
+
+def _text_request(t_lens, t_ptrs, n_cap, num_caps, flags):
+  """The level-1 text request of encode_group: all captions + paragraphs (t_lens, t_ptrs in that
+  order), or — with `flags` (text_prefix_flags of the group) — the kept captions + paragraphs with
+  every shared first caption as a prefix alias of its paragraph.  The step plan is that of the
+  ORIGINAL sequences — the caller's split plan, else `own_plan`, the original sequences' own counts,
+  which every request with aliases carries whether or not a split plan was given when it was built (a
+  kept plan may be served later without one): which kernel serves step t is chosen from the active
+  count of step t, and must not move because sequences left the request."""
+  req = dict(lens=t_lens, ptrs=t_ptrs, out_rows=None, aliases=None, n_out=None, own_plan=None, n_alias=0)
+  if flags is None:
+    return req
+  if len(t_lens) - n_cap != len(flags):
+    raise ValueError('encode_group: one prefix flag per video of the group')
+  kept, (vid, a_len, a_row) = text_prefix_aliases(t_lens[:n_cap], t_lens[n_cap:], num_caps, flags)
+  if len(vid) == 0:
+    return req
+  sel = np.concatenate([kept, n_cap + np.arange(len(t_lens) - n_cap, dtype=np.int64)])
+  req.update(lens=t_lens[sel], ptrs=t_ptrs[sel], out_rows=sel, aliases=(len(kept) + vid, a_len, a_row),
+             n_out=len(t_lens), n_alias=len(vid), own_plan=ops.step_counts(t_lens))
+  return req
+
+
+def encode_group(model, group, contextual_model=True, device=None, plan=None, step_plan=None, stage=None,
+                 share=None, plan_key=None):
   """Encode a list of loader batches (12-tuples) as ONE super-batch.  Returns a dict of device
   tensors: the six un-normalised embedding matrices plus their L2-normalised versions, rows in
   loader order.  Arithmetic per sequence is identical to per-batch encoding (sequences are
@@ -302,11 +458,24 @@ def encode_group(model, group, contextual_model=True, device=None, plan=None, st
   `stage`: a HostStage (encode_data): the level-1 matrices of each tower are normalised on ITS copy
   stream and start for the host as soon as that tower's level-1 output is final — the visual
   tower's while the text tower's few-sequence tail still steps, the text tower's under level 2 —
-  instead of after the whole pass (the values do not depend on it)."""
+  instead of after the whole pass (the values do not depend on it).
+  `share`: the PrefixCheck of this group when the caller has it (encode_data_device checks all its
+  groups in front of the first launch), False = encode every caption, None = decided and checked here;
+  `plan_key`: _plan_key(group) when the caller has computed it.  The returned dict's 'n_alias' counts
+  the first captions that were pooled from their paragraph's rows, 'n_cap' all captions."""
   device = device or torch.device('cuda', torch.cuda.current_device())
   sp = step_plan or {}
-  if plan is not None and plan.get('key') == _plan_key(group) and GROUP_TOWERS[0] and not TWO_STREAMS[0]:
-    return _encode_group_planned(model, group, contextual_model, device, plan, sp, stage)
+  share_on = share is not False and _share_on(model)
+  if plan is not None:
+    plan_key = plan_key or _plan_key(group)
+    if (plan.get('key') == plan_key and plan.get('share') == share_on and GROUP_TOWERS[0] and
+        not TWO_STREAMS[0]):
+      return _encode_group_planned(model, group, contextual_model, device, plan, sp, stage)
+  check = None
+  if share_on:
+    check = share if share is not None else _prefix_checks([group], device)[0]
+  # (tables only with sharing on, i.e. in the grouped schedule below: the other schedules build their own)
+  tables = check if check is not None and check.t_lens is not None else None
   clips_l, caps_l, vids_l, pars_l = [], [], [], []
   len_clip, len_cap, len_vid, len_par = [], [], [], []
   num_clips, num_caps = [], []
@@ -347,14 +516,15 @@ def encode_group(model, group, contextual_model=True, device=None, plan=None, st
     caps_l.append(_dev_seq(b[1], device, torch.int64))
     pars_l.append(_dev_seq(b[3], device, torch.int64))
     len_clip.append(_lens_i64(b[4]))
-    len_cap.append(_lens_i64(b[5]))
     len_vid.append(_lens_i64(b[6]))
-    len_par.append(_lens_i64(b[7]))
+    if tables is None:
+      len_cap.append(_lens_i64(b[5]))
+      len_par.append(_lens_i64(b[7]))
     num_clips.extend(b[8])
     num_caps.extend(b[9])
   n_clip = int(sum(len(l) for l in len_clip))
-  n_cap = int(sum(len(l) for l in len_cap))
   n_vid = len(num_clips)
+  n_cap = int(sum(len(l) for l in len_cap)) if tables is None else len(tables.t_lens) - n_vid
   if n_clip != sum(num_clips) or n_cap != sum(num_caps):
     raise ValueError('batch contract violated: sum(num_clips) != number of clip rows')
 
@@ -372,6 +542,7 @@ def encode_group(model, group, contextual_model=True, device=None, plan=None, st
     return enc.rnn.forward_ptrs(counts, Hin, device, x_ptrs=x_ptrs, h0_ptrs=h0, step_plan=sp.get(tower))
 
   n = ops.l2norm_rows
+  n_alias = 0
 
   def visual_tower():
     # level 1: clips of all batches, then whole-video streams of all batches (same weights)
@@ -413,19 +584,29 @@ def encode_group(model, group, contextual_model=True, device=None, plan=None, st
     # The two towers are independent: step t of both level-1 encoders shares one launch
     # (cmhse_gru_pool_fwd_multi), then step t of both level-2 encoders.
     v_ptrs = ops.seq_row_ptrs_many(clips_l + vids_l)
-    t_ptrs = ops.seq_row_ptrs_many(caps_l + pars_l)
+    if tables is None:
+      t_ptrs = ops.seq_row_ptrs_many(caps_l + pars_l)
+      t_lens = np.concatenate(len_cap + len_par)
+    else:       # (resident tokens: the tensors of caps_l / pars_l are the loader's own)
+      t_ptrs, t_lens = tables.t_ptrs, tables.t_lens
     # The visual chain (<= 80 frames) ends long before the text chain (paragraphs of hundreds of
     # tokens, a handful of sequences per step by then): the text tail continues on a separate (own hardware queue; ops.stream_set)
     # side stream while the visual attention pass runs on this one, instead of after it.
     tail = _tail_stream(device) if EARLY_POOL[0] else None
-    v_lens, t_lens = np.concatenate(len_clip + len_vid), np.concatenate(len_cap + len_par)
+    v_lens = np.concatenate(len_clip + len_vid)
+    # (first captions that are a prefix of their paragraph leave the request: _text_request)
+    tr = _text_request(t_lens, t_ptrs, n_cap, num_caps if tables is None else tables.num_caps,
+                       None if check is None else check.flags)
+    n_alias = tr['n_alias']
     t_sched = None
     if plan is not None and not pull:     # resident batches: the schedules outlive this pass
       v_sched = ops.SeqSchedule(v_lens, device, x_ptrs=v_ptrs)
-      t_sched = ops.SeqSchedule(t_lens, device, tok_ptrs=t_ptrs)
+      t_sched = ops.SeqSchedule(tr['lens'], device, tok_ptrs=tr['ptrs'], out_rows=tr['out_rows'],
+                                aliases=tr['aliases'], n_out=tr['n_out'])
       plan.clear()
-      plan.update(key=_plan_key(group), v_sched=v_sched, t_sched=t_sched, v_lens=v_lens,
-                  t_lens=t_lens, v_ptrs=v_ptrs, t_ptrs=t_ptrs, img_dim=img_dim, n_clip=n_clip,
+      plan.update(key=plan_key, share=share_on, v_sched=v_sched, t_sched=t_sched, v_lens=v_lens,
+                  t_lens=tr['lens'], v_ptrs=v_ptrs, t_ptrs=tr['ptrs'], t_own_plan=tr['own_plan'],
+                  n_alias=tr['n_alias'], img_dim=img_dim, n_clip=n_clip,
                   n_cap=n_cap, n_vid=n_vid, num_clips=np.asarray(num_clips, dtype=np.int64),
                   num_caps=np.asarray(num_caps, dtype=np.int64),
                   batch_sizes=[len(b[8]) for b in group], keep=(clips_l, vids_l, caps_l, pars_l))
@@ -433,9 +614,11 @@ def encode_group(model, group, contextual_model=True, device=None, plan=None, st
     (vis, _), (txt, _) = ops.gru_pool_fwd_multi([
         clip_rnn.request_ptrs(v_lens, img_dim, device, x_ptrs=v_ptrs,
                               sched=v_sched, step_events=v_events, step_plan=sp.get('v1')),
-        txt_rnn.request_ptrs(t_lens, table.shape[1], device,
-                             tok_ptrs=t_ptrs, table=table, sched=t_sched,
-                             step_plan=sp.get('t1'))], tail_stream=tail, ready_events=ready)
+        txt_rnn.request_ptrs(tr['lens'], table.shape[1], device,
+                             tok_ptrs=tr['ptrs'], table=table, sched=t_sched,
+                             step_plan=sp.get('t1') if sp.get('t1') is not None else tr['own_plan'],
+                             out_rows=tr['out_rows'], aliases=tr['aliases'], n_out=tr['n_out'])],
+        tail_stream=tail, ready_events=ready)
     clip_emb, vid_ctx = vis[:n_clip], vis[n_clip:]
     cap_emb, para_ctx = txt[:n_cap], txt[n_cap:]
     lvl1 = None if stage is None else stage.level1(ready, clip_emb, cap_emb, vid_ctx, para_ctx)
@@ -462,7 +645,7 @@ def encode_group(model, group, contextual_model=True, device=None, plan=None, st
     out_txt = text_tower()
   return dict(vid_emb=out_vis[0], para_emb=out_txt[0], clip_emb=out_vis[1], cap_emb=out_txt[1],
               vid_ctx=out_vis[2], para_ctx=out_txt[2], n_vid=n_vid,
-              batch_sizes=[len(b[8]) for b in group])
+              batch_sizes=[len(b[8]) for b in group], n_alias=n_alias, n_cap=n_cap)
 
 
 def _encode_group_planned(model, group, contextual_model, device, plan, sp, stage=None):
@@ -479,7 +662,8 @@ def _encode_group_planned(model, group, contextual_model, device, plan, sp, stag
       clip_rnn.request_ptrs(plan['v_lens'], plan['img_dim'], device, x_ptrs=plan['v_ptrs'],
                             sched=plan['v_sched'], step_plan=sp.get('v1')),
       txt_rnn.request_ptrs(plan['t_lens'], table.shape[1], device, tok_ptrs=plan['t_ptrs'],
-                           table=table, sched=plan['t_sched'], step_plan=sp.get('t1'))],
+                           table=table, sched=plan['t_sched'],
+                           step_plan=sp.get('t1') if sp.get('t1') is not None else plan['t_own_plan'])],
       tail_stream=tail, ready_events=ready)
   clip_emb, vid_ctx = vis[:n_clip], vis[n_clip:]
   cap_emb, para_ctx = txt[:n_cap], txt[n_cap:]
@@ -499,7 +683,7 @@ def _encode_group_planned(model, group, contextual_model, device, plan, sp, stag
   if lvl1 is None:
     lvl1 = dict(clip_emb=n(clip_emb), cap_emb=n(cap_emb), vid_ctx=n(vid_ctx), para_ctx=n(para_ctx))
   return dict(vid_emb=n(vid_emb), para_emb=n(para_emb), n_vid=plan['n_vid'],
-              batch_sizes=plan['batch_sizes'], **lvl1)
+              batch_sizes=plan['batch_sizes'], n_alias=plan['n_alias'], n_cap=n_cap, **lvl1)
 
 
 @contextlib.contextmanager
@@ -580,11 +764,26 @@ def encode_data_device(opt, model, data_loader, log_step=10, logging=print, cont
     groups = _group_batches(batches, superbatch_bytes)
     if step_plan is None and len(groups) > 1:       # (one group: its own step counts ARE the split's)
       step_plan = split_step_plan(batches)
+    # Prefix sharing: the token check of ALL groups in front of the first launch (one read-back while
+    # the GPU has nothing queued; a read-back in a later group would stall a host that runs a group
+    # ahead).  A group whose cached plan is still valid was checked when that plan was built.
+    keys = [None if plan is None else _plan_key(g) for g in groups]
+    share = [False] * len(groups)
+    if _share_on(model):
+      share = [None] * len(groups)     # (None: served from the group's valid plan)
+      todo = [gi for gi in range(len(groups))
+              if plan is None or not (plan.get(gi, {}).get('key') == keys[gi] and plan[gi].get('share'))]
+      device = torch.device('cuda', torch.cuda.current_device())
+      for gi, check in zip(todo, _prefix_checks([groups[gi] for gi in todo], device)):
+        share[gi] = check
+    n_alias = n_caps = 0
     for gi, group in enumerate(groups):
       model.logger = val_logger                     # evaluation.py:99
       enc = encode_group(model, group, contextual_model,
                          plan=None if plan is None else plan.setdefault(gi, {}), step_plan=step_plan,
-                         stage=stage)
+                         stage=stage, share=share[gi], plan_key=keys[gi])
+      n_alias += enc['n_alias']
+      n_caps += enc['n_cap']
       if stage is not None:
         stage.put({k: enc[k] for k in outs})     # (what left early is skipped)
       for k in outs:
@@ -607,6 +806,7 @@ def encode_data_device(opt, model, data_loader, log_step=10, logging=print, cont
         pending.append((group, enc['batch_sizes'], loss_dev.cpu(), None, None))
         flush()
   cat = {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in outs.items()}
+  SHARE_STATS.update(aliases=n_alias, captions=n_caps)      # of the whole call
   if defer_logging:
     return cat, num_clips_total, cur_vid_total, flush
   return cat, num_clips_total, cur_vid_total

@@ -95,7 +95,7 @@ def tune(name, value=-1):
   are initialised from.  Names: tiny_max_seqs, mid_max_seqs, mid_units, mid_waves,
   tall_tile_min_wgs, mid_tall_min_seqs, bwd_mid_max_seqs, bwd_split_min_seqs, bwd_tail_min_steps,
   fwd_tail_min_steps, bwd_chunk_rows, xproj_chunk_rows, tn_rows_bm, chain_min_steps, early_xproj,
-  chain_tall_min_wgs, pull_waves, resident_timeout_ms, tok_table (include/cmhse_hip.h)."""
+  chain_tall_min_wgs, pull_waves, resident_timeout_ms, tok_table, share_prefix (include/cmhse_hip.h)."""
   ctx = TuneContext.current()
   if ctx is not None:
     return ctx.tune(name, value)
@@ -227,10 +227,13 @@ class SeqSchedule(object):
   `pack_padded_sequence(..., lens.tolist())` (/root/reference/layers.py:94-97): sequences sorted
   longest-first, so the sequences still active at step t are the prefix [0, step_count[t]).
   All small per-sequence arrays go to the device in ONE copy.
+  `out_rows`: the output row of every sequence (input order) when the sequences are not rows 0..S-1 of
+  `out` in input order; `aliases`: (src, length, out_row) int arrays — prefix aliases
+  (cmhse_seq_batch.n_alias), src an index into `lens` (input order); `n_out`: rows of `out` (default S).
   """
 
   def __init__(self, lens, device, x_ptrs=None, tok_ptrs=None, h0_ptrs=None,
-               out_rows_are_starts=False, src_ptrs=None):
+               out_rows_are_starts=False, src_ptrs=None, out_rows=None, aliases=None, n_out=None):
     lens = np.asarray(lens, dtype=np.int64).reshape(-1)
     if lens.size == 0 or lens.min() < 1:
       raise ValueError('all sequence lengths must be >= 1 (pack_padded_sequence contract)')
@@ -256,9 +259,11 @@ class SeqSchedule(object):
     self.lens_sorted = ls
 
     # one packed metadata buffer:
-    #   [x_rows u64 | h0_rows u64 | (src_rows u64) | lens i32 | out_row i32 | step_off i32]
+    #   [x_rows u64 | h0_rows u64 | (src_rows u64) | lens i32 | out_row i32 | step_off i32 |
+    #    (alias_src i32 | alias_len i32 | alias_out_row i32)]
     n64 = (3 if src_ptrs is not None else 2) * S
-    n32 = 2 * S + (Tmax + 1)
+    n_alias = 0 if aliases is None else len(aliases[0])
+    n32 = 2 * S + (Tmax + 1) + 3 * n_alias
     buf = np.zeros(n64 * 8 + n32 * 4, dtype=np.uint8)
     v64 = buf[:n64 * 8].view(np.uint64)
     v32 = buf[n64 * 8:].view(np.int32)
@@ -273,9 +278,29 @@ class SeqSchedule(object):
       # CMHSE_POOL_ALL: sequence i (input order) owns output rows [start_i, start_i + len_i)
       starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
       v32[S:2 * S] = starts[order]
+    elif out_rows is not None:
+      v32[S:2 * S] = np.asarray(out_rows, dtype=np.int64)[order]
     else:
       v32[S:2 * S] = order
-    v32[2 * S:] = step_off
+    v32[2 * S:2 * S + Tmax + 1] = step_off
+    self.n_alias, self.n_out = n_alias, (S if n_out is None else int(n_out))
+    self.alias_host = None
+    if n_alias:
+      a_src, a_len, a_row = (np.asarray(a, dtype=np.int64).reshape(-1) for a in aliases)
+      rank = np.empty(S, dtype=np.int64)      # input index -> sorted index
+      rank[order] = np.arange(S, dtype=np.int64)
+      a_src = rank[a_src]
+      if (a_len < 1).any() or (a_len > ls[a_src]).any():
+        raise ValueError('a prefix alias is longer than its source sequence')
+      al = v32[2 * S + Tmax + 1:].reshape(3, n_alias)
+      al[0], al[1], al[2] = a_src, a_len, a_row
+      self.alias_host = np.ascontiguousarray(al[:2])      # the copies the library validates
+    if out_rows is not None or n_alias:
+      # the kernels write the rows these arrays name without looking: each row of `out` exactly once
+      rows = v32[S:2 * S] if not n_alias else np.concatenate([v32[S:2 * S], v32[2 * S + Tmax + 1 + 2 * n_alias:]])
+      if (len(rows) != self.n_out or int(rows.min()) < 0 or int(rows.max()) >= self.n_out or
+          (np.bincount(rows, minlength=self.n_out) != 1).any()):
+        raise ValueError('out_rows and the alias rows must name each of the n_out output rows exactly once')
     self.meta = upload(buf, device)
     base = self.meta.data_ptr()
     self.p_rows = base
@@ -284,6 +309,7 @@ class SeqSchedule(object):
     self.p_lens = base + n64 * 8
     self.p_out_row = self.p_lens + S * 4
     self.p_step_off = self.p_out_row + S * 4
+    self.p_alias = self.p_step_off + (Tmax + 1) * 4 if n_alias else None
     self.is_tokens = x_ptrs is None
 
 
@@ -536,23 +562,49 @@ def rows_differ(pairs):
   return bool(flag.item())
 
 
+def tok_prefix_check(a_ptrs, b_ptrs, a_len, b_len, device):
+  """cmhse_tok_prefix_check: for n pairs of token sequences resident on `device` (base addresses as
+  uint64 NumPy, lengths) an int32 device tensor [n]: 1 where the first a_len ids at a_ptrs equal the first
+  ids at b_ptrs and b_len >= a_len.  Asynchronous on the current stream; the caller reads it back."""
+  n = len(a_ptrs)
+  buf = np.empty(n * 24, dtype=np.uint8)
+  v64 = buf[:n * 16].view(np.uint64)
+  v32 = buf[n * 16:].view(np.int32)
+  v64[:n], v64[n:] = a_ptrs, b_ptrs
+  v32[:n], v32[n:] = a_len, b_len
+  meta = upload(buf, device)
+  flags = torch.empty(n, dtype=torch.int32, device=device)
+  base = meta.data_ptr()
+  rc = _lib.load().cmhse_tok_prefix_check(n, base, base + 8 * n, base + 16 * n, base + 20 * n,
+                                          flags.data_ptr(), _stream())
+  _lib.check(rc, 'cmhse_tok_prefix_check')
+  return flags
+
+
 def _prepare_fwd(weights, pool_mode, lens, I, H, device, x_ptrs=None, tok_ptrs=None,
                  emb_table=None, h0_ptrs=None, out=None, save_for_backward=False,
-                 constant_input=False, sched=None, step_events=None, side=True, step_plan=None):
+                 constant_input=False, sched=None, step_events=None, side=True, step_plan=None,
+                 out_rows=None, aliases=None, n_out=None):
   """Build the ctypes request of one cmhse_gru_pool_fwd call.  Returns (job dict, timer meta).
   `sched`: a prebuilt SeqSchedule for these sequences (else built here); `step_events`:
   {step: torch.cuda.Event} the step's launch must wait for (chunked upload, pull_steps);
   `step_plan`: active sequences per time step of the WHOLE set these sequences are a share of
   (step_counts() of all its lengths; cmhse_seq_batch.step_plan_host) — the kernel kind of every step
-  is then chosen from it, so a sequence is encoded bit for bit the same in any share."""
+  is then chosen from it, so a sequence is encoded bit for bit the same in any share.
+  `out_rows`, `aliases`, `n_out`: SeqSchedule's (a prebuilt `sched` carries its own): prefix aliases,
+  attention-pooled inference requests only."""
   lib = _lib.load()
   if sched is None:
     sched = SeqSchedule(lens, device, x_ptrs, tok_ptrs, h0_ptrs,
-                        out_rows_are_starts=(pool_mode == POOL_ALL))
+                        out_rows_are_starts=(pool_mode == POOL_ALL), out_rows=out_rows, aliases=aliases,
+                        n_out=n_out)
   S = sched.S
   if out is None:
-    n_out = sched.sum_T if pool_mode == POOL_ALL else S
+    n_out = sched.sum_T if pool_mode == POOL_ALL else sched.n_out
     out = torch.empty(n_out, H, dtype=torch.float32, device=device)
+  elif pool_mode != POOL_ALL and (out.dim() != 2 or out.shape[0] < sched.n_out or out.shape[1] != H or
+                                  out.dtype != torch.float32 or not out.is_contiguous()):
+    raise ValueError('out must be a contiguous float32 [>= %d, %d] tensor' % (sched.n_out, H))
   mode_flags = pool_mode | (SAVE_FOR_BACKWARD if save_for_backward else 0)
   if math_mode() == 'bf16x3' and not save_for_backward:
     mode_flags |= MATH_BF16X3
@@ -585,6 +637,13 @@ def _prepare_fwd(weights, pool_mode, lens, I, H, device, x_ptrs=None, tok_ptrs=N
   b.h0_rows = sched.p_h0
   b.lens, b.out_row, b.step_off = sched.p_lens, sched.p_out_row, sched.p_step_off
   b.step_count_host = sched.step_count_host.ctypes.data
+  if sched.n_alias:
+    b.n_alias = sched.n_alias
+    b.alias_src = sched.p_alias
+    b.alias_len = sched.p_alias + 4 * sched.n_alias
+    b.alias_out_row = sched.p_alias + 8 * sched.n_alias
+    b.alias_src_host = sched.alias_host[0].ctypes.data
+    b.alias_len_host = sched.alias_host[1].ctypes.data
   if step_plan is not None and not save_for_backward:
     plan = np.zeros(sched.Tmax, dtype=np.int32)
     sp = np.asarray(step_plan, dtype=np.int32)[:sched.Tmax]

@@ -135,6 +135,25 @@ typedef struct cmhse_seq_batch {
                                a sequence is encoded bit for bit the same whatever share of the split
                                it is encoded with (parallel_eval: integer ranks identical for any
                                number of ranks).  NULL = the batch's own counts */
+  /* Prefix aliases (0 / NULL = none): extra OUTPUT rows pooled from the first steps of sequences of this
+   * batch.  When sequence a is a prefix of sequence b (same input rows, both from h0 = 0: a video's first
+   * caption and its paragraph, activity_net/data.py:78), the hidden states and attention energies of a
+   * ARE those of b's first len_a steps, so a is left out of the batch and alias i stands in for it:
+   *   out[alias_out_row[i], :] = attention pooling of steps 0 .. alias_len[i]-1 of sequence alias_src[i]
+   * (alias_src: SORTED index, the index of lens / out_row), evaluated exactly as for a real sequence of
+   * that length: the same bits.  CMHSE_POOL_ATTN inference requests only (CMHSE_ERR_ARG with another
+   * pooling or CMHSE_SAVE_FOR_BACKWARD), every alias_src in [0, S) and 1 <= alias_len <= lens[alias_src]
+   * (CMHSE_ERR_ARG otherwise).  The *_host copies are what the call validates (it never reads device
+   * memory on the host); the kernels read the device copies, which must hold the same values (a device
+   * length beyond its source is clamped to it).  `out` then has more rows than S: out_row and
+   * alias_out_row together name each of them once.  The caller keeps the step plan of the ORIGINAL
+   * sequences in step_plan_host, so that every remaining step is served by the kernel it had with them. */
+  int32_t n_alias;
+  const int32_t* alias_src;     /* [n_alias] device */
+  const int32_t* alias_len;     /* [n_alias] device */
+  const int32_t* alias_out_row; /* [n_alias] device */
+  const int32_t* alias_src_host; /* HOST [n_alias] */
+  const int32_t* alias_len_host; /* HOST [n_alias] */
 } cmhse_seq_batch;
 
 /* Bytes of workspace cmhse_gru_pool_fwd needs for this batch: the time-major packed hidden states
@@ -248,6 +267,14 @@ int cmhse_push_rows(const void* src, void* dst_pinned, size_t bytes, int32_t wor
  * 160-213) use it to make sure the NumPy arrays they are handed still hold what encode_data wrote
  * before they report the ranking encode_data already queued on the device copies.  Asynchronous. */
 int cmhse_rows_differ(const void* a, const void* b, size_t bytes, int32_t* flag, void* stream);
+
+/* Is token sequence a a prefix of token sequence b?  For each of n pairs: flags[i] = 1 iff
+ * b_len[i] >= a_len[i] and the first a_len[i] int64 ids at a_rows[i] and at b_rows[i] (device addresses,
+ * as cmhse_seq_batch.tok_rows) are equal, else 0.  Raw ids are compared (the encoders clamp both sides
+ * to [0, vocab) alike).  The precondition of the prefix aliases above, checked on the data of every
+ * call: one wave per pair, all arrays on the device, flags int32 [n].  Asynchronous. */
+int cmhse_tok_prefix_check(int32_t n, const uint64_t* a_rows, const uint64_t* b_rows, const int32_t* a_len,
+                           const int32_t* b_len, int32_t* flags, void* stream);
 
 /* The padding half of the loader's collate_fn (activity_net/data.py:114-150, didemo_dev/data.py:
  * 133-165) as an index kernel: S ragged sequences stored back to back, row r of sequence s at
@@ -630,6 +657,11 @@ int cmhse_timer_tiled(void* timer, float* ms_host, double* flops_host, double* b
  *                             share it) and its steps read x_t W_ih^T from G[token]; 0 = off (results
  *                             identical).  Read when the workspace is sized
  *                             (cmhse_gru_pool_workspace_tok) and when the call starts
+ *   "share_prefix"         1  (read by the host glue, cmhse_amd/evaluation.py, not by the library) 1: the
+ *                             text tower of a validation pass leaves out every video's first caption whose
+ *                             tokens are a prefix of its paragraph's (cmhse_tok_prefix_check) and pools it
+ *                             from the paragraph's rows (cmhse_seq_batch.n_alias); 0 = encode every caption
+ *                             (results identical)
  *   "multi_step_off"       0  (not a crossover, and per DEVICE rather than per context) 1 while the
  *                             multi-step kernels are switched off on the calling thread's current device
  *                             after an acknowledged timeout (cmhse_async_status below); readable, and
