@@ -6,6 +6,9 @@
 //                         the arg-max column — the N x M matrix never reaches HBM.  Its top-1 key,
 //                         operand rows and XCD-grouped deal of the tiles are score_tile.hpp's, shared
 //                         with topk.hip and group.hip.
+//   cmhse_sim_rank_labelled  the same ranking against any set of positives per query, any gallery
+//                         size: a threshold pass over the (query, positive) pairs in the place of the
+//                         diagonal pass, then the same counting pass without the excluded column.
 //   cmhse_cosine_sim      loss.cosine_sim       (/root/reference/loss.py:12-13)
 //   cmhse_contrastive_fwd loss.ContrastiveLoss.forward (/root/reference/loss.py:86-117)
 //
@@ -30,7 +33,9 @@ constexpr int kSimBM = 128;
 constexpr int kSimBN = 128;
 constexpr int kSimSmallMax = 512;   // stored-score matrices up to this size use 64 x 64 tiles
 
-enum { kSimDiag = 0, kSimRank = 1, kSimStore = 2 };
+// kSimLabel: the counting pass of cmhse_sim_rank_labelled — kSimRank's, except that p.diag holds a
+// per-row threshold (the best positive's score) instead of the diagonal and no column is excluded.
+enum { kSimDiag = 0, kSimRank = 1, kSimStore = 2, kSimLabel = 3 };
 
 struct SimParams {
   const float* A;  // [N, D]
@@ -82,6 +87,7 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
         (static_cast<uint64_t>(__builtin_amdgcn_s_getreg((31 << 11) | 20)) << 32);
   }
 #endif
+  constexpr bool COUNT = MODE == kSimRank || MODE == kSimLabel;   // the counting passes
   SimParams p = p_;
   if (p.blk_off != nullptr) {
     const int off = p.blk_off[blockIdx.y];
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
   if (MODE == kSimDiag) {
     i0 = blockIdx.x * BM;
     j0 = p.row0 + i0;  // the column block that holds this row block's diagonal
-  } else if (MODE == kSimRank && p.group > 0) {
+  } else if (COUNT && p.group > 0) {
     // counting pass: the XCD-grouped deal (score_tile.hpp)
     const TileIdx t = xcd_deal_tile(blockIdx.x, p.group, p.n_tiles);
     j0 = t.ct * BN;
@@ -131,13 +137,13 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
   // round trips per lane, ~50 of the 62 us the epilogue took — profiles/r04_sim_kernel_trace.txt);
   // they go through LDS once the tile buffers are free
   float my_diag = 0.f;
-  if (MODE == kSimRank && tid < BM) my_diag = (i0 + tid < p.nrows) ? p.diag[i0 + tid] : 0.f;
+  if (COUNT && tid < BM) my_diag = (i0 + tid < p.nrows) ? p.diag[i0 + tid] : 0.f;
   SIM_MARK(1);
   SIM_CLOCK(5);
   nt_phase<BM, BN, TS, TS, TS, TS - 1, VEC>(smem, ar, av, br, bv, p.D, wm * 32 * TS, b_row0, acc);
   SIM_MARK(3);
   SIM_CLOCK(7);
-  if (MODE == kSimRank) {
+  if (COUNT) {
     // (what is left of the epilogue is ~12 us of vector / scalar work on its own and 48 beside two
     // workgroups inside their MFMA loops on the same SIMDs; raising its wave priority changes
     // nothing: 404 / 407 us per launch)
@@ -184,7 +190,7 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
           const int j = j0 + b_row0[ns] + acc_col(lane);
           const float v = acc[ms][ns][r];
           const bool valid = rok && j < p.M;
-          const unsigned long long gt = __ballot(valid && j != gi && v > dii);
+          const unsigned long long gt = __ballot(valid && (MODE == kSimLabel || j != gi) && v > dii);
           cnt += __popc(hi ? static_cast<unsigned>(gt >> 32) : static_cast<unsigned>(gt));
           ob[ns] = valid ? ordered_bits(v) : 0u;
           obmax = ob[ns] > obmax ? ob[ns] : obmax;
@@ -217,6 +223,97 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
 __global__ void top1_finalize_kernel(const score_key_t* key, int32_t* top1, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) top1[i] = key_index(key[i]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// cmhse_sim_rank_labelled: the threshold pass (in the place of sim_kernel<kSimDiag>) and the decoding
+// of its keys.  The (query, positive) pairs of the stripe's CSR, in CSR order, are cut into tiles of
+// 128: operand A row r of a tile is the query of pair r, operand B row c the gallery row of pair c,
+// and the wanted scores are the tile's diagonal — out of nt_phase like every score of the counting
+// pass, so bit-identical to what that pass compares them with.  Each goes into its query's 64-bit
+// key by atomicMax (larger score, then smaller gallery index: independent of tiling and scheduling).
+// ---------------------------------------------------------------------------------------------
+struct PairParams {
+  const float* A;            // [N, D]
+  const float* B;            // [M, D]
+  int32_t M, D, row0, nrows, n_pairs;
+  const int32_t* pos_off;    // [nrows + 1] device copy
+  const int32_t* pos_idx;    // [n_pairs]   device copy
+  score_key_t* thrkey;       // [nrows], zeroed
+};
+
+constexpr size_t kPairSmem = TileSmem<kSimBM, kSimBN>::kBytes + 2 * kSimBM * sizeof(int32_t);
+
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void pair_threshold_kernel(const PairParams p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  // behind nt_phase's tile buffers: the query (local stripe row; -1 past the last pair) and the
+  // gallery row of each pair of the tile, for the lanes that end up holding the diagonal
+  int32_t* s_query = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(smem) + TileSmem<kSimBM, kSimBN>::kBytes);
+  int32_t* s_pos = s_query + kSimBM;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int srow = tid >> 2;
+  const int g0 = blockIdx.x * kSimBM;   // the tile's first pair
+  rowaddr_t ar[kSimBM / 64], br[kSimBN / 64];
+  bool av[kSimBM / 64], bv[kSimBN / 64];
+#pragma unroll
+  for (int i = 0; i < kSimBM / 64; ++i) {
+    const int g = g0 + srow + 64 * i;
+    const bool ok = g < p.n_pairs;
+    int q = 0, c = 0;
+    if (ok) {
+      // The query of pair g: the last q with pos_off[q] <= g.  Every list holds a positive, so
+      // pos_off[q] - q never decreases and ends at n_pairs - nrows: q lies in [g - (n_pairs - nrows), g]
+      // (one positive per query: no search at all).  Every index read lies in [0, nrows), whatever
+      // the arrays hold.
+      int lo = g - (p.n_pairs - p.nrows), hi = (g < p.nrows - 1) ? g : p.nrows - 1;
+      lo = lo < 0 ? 0 : lo;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (p.pos_off[mid] <= g) lo = mid; else hi = mid - 1;
+      }
+      q = lo;
+      // (validated on the host copy; the clamp keeps a device copy that differs from it inside B)
+      c = p.pos_idx[g];
+      c = c < 0 ? 0 : (c < p.M ? c : p.M - 1);
+    }
+    ar[i] = row_addr(p.A + static_cast<int64_t>(p.row0 + q) * p.D);
+    br[i] = row_addr(p.B + static_cast<int64_t>(c) * p.D);
+    av[i] = bv[i] = ok;
+    if ((tid & 3) == 0) {
+      s_query[srow + 64 * i] = ok ? q : -1;
+      s_pos[srow + 64 * i] = c;
+    }
+  }
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int ms = 0; ms < 2; ++ms)
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns) acc[ms][ns] = zero16();
+  const int b_row0[2] = {wn * 64, wn * 64 + 32};
+  // (its barriers also order the s_query / s_pos writes above before the reads below)
+  nt_phase<kSimBM, kSimBN, 2, 2, 2, 1, VEC>(smem, ar, av, br, bv, p.D, wm * 64, b_row0, acc);
+  if (wm != wn) return;   // (wave-uniform) no diagonal in this wave's 64 x 64
+#pragma unroll
+  for (int ms = 0; ms < 2; ++ms) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (acc_row(r, lane) != acc_col(lane)) continue;
+      const int lr = wm * 64 + ms * 32 + acc_row(r, lane);   // pair g0 + lr: row and column of the tile
+      const int q = s_query[lr];
+      if (q >= 0) atomicMax(&p.thrkey[q], score_key(acc[ms][ms][r], s_pos[lr]));
+    }
+  }
+}
+
+__global__ void label_decode_kernel(const score_key_t* key, float* thr, int32_t* best_pos, float* best_score, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const score_key_t k = key[i];
+  thr[i] = key_score(k);
+  best_pos[i] = key_index(k);
+  if (best_score) best_score[i] = key_score(k);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -420,6 +517,81 @@ extern "C" int cmhse_sim_rank(const float* A, const float* B, int32_t N, int32_t
                               void* workspace, size_t workspace_bytes, void* stream_) {
   return cmhse_sim_rank_ex(A, B, N, M, D, row0, nrows, rank, top1, workspace, workspace_bytes,
                            stream_, nullptr);
+}
+
+extern "C" size_t cmhse_sim_rank_labelled_workspace(int32_t nrows, int32_t n_pairs) {
+  if (nrows <= 0 || n_pairs < nrows) return 0;   // (n_pairs: every query has a positive)
+  return align256(static_cast<size_t>(nrows) * sizeof(float)) +
+         align256(2 * static_cast<size_t>(nrows) * sizeof(score_key_t));
+}
+
+extern "C" int cmhse_sim_rank_labelled(const float* A, const float* B, int32_t N, int32_t M, int32_t D,
+                                       int32_t row0, int32_t nrows, const int32_t* pos_off_host,
+                                       const int32_t* pos_idx_host, const int32_t* pos_off,
+                                       const int32_t* pos_idx, int32_t n_pairs, int32_t* rank,
+                                       int32_t* top1, int32_t* best_pos, float* best_score,
+                                       void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!A || !B) return CMHSE_ERR_ARG;
+  if (N <= 0 || M <= 0 || D <= 0) return CMHSE_ERR_ARG;
+  if (row0 < 0 || nrows < 0 || static_cast<int64_t>(row0) + nrows > N) return CMHSE_ERR_ARG;
+  if (nrows == 0) return n_pairs == 0 ? CMHSE_OK : CMHSE_ERR_ARG;
+  if (!pos_off_host || !pos_idx_host || !pos_off || !pos_idx || n_pairs < nrows) return CMHSE_ERR_ARG;
+  // the labels, in full, on the host copy: nothing is launched on a list that fails
+  if (pos_off_host[0] != 0 || pos_off_host[nrows] != n_pairs) return CMHSE_ERR_ARG;
+  for (int32_t i = 0; i < nrows; ++i)
+    if (pos_off_host[i + 1] <= pos_off_host[i]) return CMHSE_ERR_ARG;
+  for (int32_t e = 0; e < n_pairs; ++e)
+    if (pos_idx_host[e] < 0 || pos_idx_host[e] >= M) return CMHSE_ERR_ARG;
+  if (!rank || !top1 || !best_pos || !workspace) return CMHSE_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
+      workspace_bytes < cmhse_sim_rank_labelled_workspace(nrows, n_pairs))
+    return CMHSE_ERR_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  SimParams p;
+  p.A = A;
+  p.B = B;
+  p.N = N;
+  p.M = M;
+  p.D = D;
+  p.row0 = row0;
+  p.nrows = nrows;
+  p.n_tiles = (M + kSimBN - 1) / kSimBN;
+  p.diag = static_cast<float*>(workspace);   // the thresholds
+  p.top1key = reinterpret_cast<score_key_t*>(
+      static_cast<char*>(workspace) + align256(static_cast<size_t>(nrows) * sizeof(float)));
+  p.rank = rank;
+  p.scores = nullptr;
+  p.blk_off = nullptr;
+  p.blk_stride = 0;
+  const int m_tiles = (nrows + kSimBM - 1) / kSimBM;
+  const XcdDeal deal = xcd_deal(m_tiles, p.n_tiles);
+  p.group = deal.group;
+  if (deal.blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  PairParams q;
+  q.A = A;
+  q.B = B;
+  q.M = M;
+  q.D = D;
+  q.row0 = row0;
+  q.nrows = nrows;
+  q.n_pairs = n_pairs;
+  q.pos_off = pos_off;
+  q.pos_idx = pos_idx;
+  q.thrkey = p.top1key + nrows;
+  if (hipMemsetAsync(rank, 0, sizeof(int32_t) * nrows, stream) != hipSuccess) return CMHSE_ERR_LAUNCH;
+  if (hipMemsetAsync(p.top1key, 0, 2 * sizeof(score_key_t) * nrows, stream) != hipSuccess)   // and thrkey
+    return CMHSE_ERR_LAUNCH;
+  int rc = launch_tiles(pair_threshold_kernel<true>, pair_threshold_kernel<false>, D,
+                        dim3((n_pairs + kSimBM - 1) / kSimBM), kPairSmem, stream, q);
+  if (rc != CMHSE_OK) return rc;
+  hipLaunchKernelGGL(label_decode_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream, q.thrkey,
+                     p.diag, best_pos, best_score, nrows);
+  rc = launch_tiles(sim_kernel<kSimLabel, true>, sim_kernel<kSimLabel, false>, D,
+                    dim3(static_cast<unsigned>(deal.blocks)), TileSmem<kSimBM, kSimBN>::kBytes, stream, p);
+  if (rc != CMHSE_OK) return rc;
+  hipLaunchKernelGGL(top1_finalize_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream,
+                     p.top1key, top1, nrows);
+  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }
 
 extern "C" int cmhse_cosine_sim(const float* im, const float* s, int32_t n, int32_t m, int32_t D,

@@ -1113,6 +1113,93 @@ def group_retrieve(clip_embs, cap_embs, num_clips, num_caps=None, k=10, directio
   return scores.cpu().numpy(), index.cpu().numpy().astype(numpy.int64)
 
 
+def pairs_from_ids(image_ids, caption_ids):
+  """The (image row, caption row) pairs whose ids are equal, int64 [P, 2], sorted by image row, then
+  caption row: the `pairs` of i2t_t2i_labelled from two id lists (encode_data's eighth return value
+  is the id list of its rows).  A caption whose id no image carries gives no pair.  No GPU."""
+  rows = {}
+  for c, key in enumerate(caption_ids):
+    rows.setdefault(key, []).append(c)
+  pairs = [(i, c) for i, key in enumerate(image_ids) for c in rows.get(key, ())]
+  return numpy.asarray(pairs, dtype=numpy.int64).reshape(-1, 2)
+
+
+def csr_from_pairs(pairs, n_images, n_captions):
+  """Both label sets of i2t_t2i_labelled from `pairs`, an integer [P, 2] array of (image row, caption
+  row): ((offsets, indices) image -> its captions, (offsets, indices) caption -> its images), each
+  list ascending.  ValueError for a row outside its matrix and for a row of either side that appears
+  in no pair (it would have nothing to be ranked against), naming it.  No GPU."""
+  pairs = numpy.asarray(pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs)
+  if pairs.ndim != 2 or pairs.shape[1] != 2 or not (pairs.size == 0 or numpy.issubdtype(pairs.dtype, numpy.integer)):
+    raise ValueError('pairs must be an integer [P, 2] array of (image row, caption row), got %s %r'
+                     % (pairs.dtype, pairs.shape))
+  pairs = pairs.astype(numpy.int64)
+  out = []
+  for side, other, n, n_other, name, other_name in ((0, 1, n_images, n_captions, 'image', 'caption'),
+                                                    (1, 0, n_captions, n_images, 'caption', 'image')):
+    key, val = pairs[:, side], pairs[:, other]
+    bad = (key < 0) | (key >= n)
+    if bad.any():
+      raise ValueError('pair %d: %s row %d outside [0, %d)' % (int(numpy.flatnonzero(bad)[0]), name,
+                                                               int(key[bad][0]), n))
+    counts = numpy.bincount(key, minlength=n)
+    if (counts == 0).any():
+      raise ValueError('%s row %d appears in no pair: it has no correct %s to be ranked against'
+                       % (name, int(numpy.flatnonzero(counts == 0)[0]), other_name))
+    off = numpy.zeros(n + 1, dtype=numpy.int64)
+    numpy.cumsum(counts, out=off[1:])
+    out.append((off, val[numpy.lexsort((val, key))]))
+  return out[0], out[1]
+
+
+def rank_labelled(queries, gallery, positives):
+  """i2t's report for any gallery and any set of correct answers per query: `positives` gives, for
+  every query row, the gallery rows that count as correct (a 1-D target index per query, a CSR tuple
+  (offsets, indices) or a list of per-query index lists: ops.positives_csr), and the rank of a query
+  is the rank of its best-placed positive (ops.sim_rank_labelled: matrix-free, exact fp32).
+  Returns (report, top1, ranks) in i2t's format (report_from_ranks; float64 NumPy).  GPU tensors in:
+  top1 and ranks stay int32 device tensors.  The ranking cache i2t / t2i serve from is neither read
+  nor changed."""
+  on_device = isinstance(queries, torch.Tensor) and queries.is_cuda
+  csr = ops.positives_csr(positives, len(queries), len(gallery))   # argument errors before the upload
+  q = _as_device(queries)
+  rank, top1, _ = ops.sim_rank_labelled(q, _as_device(gallery, q.device), csr)
+  host = torch.stack([rank, top1]).cpu().numpy().astype(numpy.float64)
+  if on_device:
+    return report_from_ranks(host[0]), top1, rank
+  return report_from_ranks(host[0]), host[1], host[0]
+
+
+def i2t_t2i_labelled(images, captions, pairs):
+  """i2t_t2i for matrices whose correct answers are given by `pairs`, an integer [P, 2] array of
+  (image row, caption row) — any number of rows on either side, any number of correct partners per
+  row, at least one (pairs_from_ids builds it from two id lists).  Two annotation sets scored against
+  one video set:
+
+    vid, para1, *_, ids1 = encode_data(opt, model, val_1_loader)
+    _,   para2, *_, ids2 = encode_data(opt, model, val_2_loader)
+    paras = numpy.concatenate([para1, para2])
+    (r_v2p, _, _), (r_p2v, _, _) = i2t_t2i_labelled(vid, paras, pairs_from_ids(ids1, ids1 + ids2))
+
+  Returns ((report, top1, ranks) image -> caption, the same caption -> image), each in i2t's format,
+  with one device-to-host copy; with pairs (i, i) exactly what i2t_t2i returns.  GPU tensors in: top1
+  and ranks stay int32 device tensors.  The ranking cache i2t / t2i serve from is neither read nor
+  changed."""
+  on_device = isinstance(images, torch.Tensor) and images.is_cuda
+  csr_i, csr_t = csr_from_pairs(pairs, len(images), len(captions))   # argument errors before the upload
+  v = _as_device(images)
+  p = _as_device(captions, v.device)
+  r_i, t_i, _ = ops.sim_rank_labelled(v, p, csr_i)
+  r_t, t_t, _ = ops.sim_rank_labelled(p, v, csr_t)
+  # (the two sides differ in length: one flat vector, cut on the host)
+  n, m = r_i.numel(), r_t.numel()
+  host = numpy.split(torch.cat([r_i, t_i, r_t, t_t]).cpu().numpy().astype(numpy.float64), [n, 2 * n, 2 * n + m])
+  if on_device:
+    return ((report_from_ranks(host[0]), t_i, r_i), (report_from_ranks(host[2]), t_t, r_t))
+  return ((report_from_ranks(host[0]), host[1], host[0]),
+          (report_from_ranks(host[2]), host[3], host[2]))
+
+
 def _rank_report(queries, gallery):
   rank, top1 = ops.sim_rank(_as_device(queries), _as_device(gallery))
   ranks = rank.cpu().numpy().astype(numpy.float64)      # the reference stores ranks in float64

@@ -873,6 +873,107 @@ def sim_topk(queries, gallery, k, row0=0, nrows=None):
   return scores, index
 
 
+def _label_ints(x, what):
+  """`x` as a 1-D int64 array; ValueError unless it holds integers (no bools, no floats)."""
+  if isinstance(x, torch.Tensor):
+    x = x.detach().cpu().numpy()
+  a = np.asarray(x)
+  if a.ndim != 1:
+    raise ValueError('%s must be 1-D, got shape %r' % (what, a.shape))
+  if a.size and not np.issubdtype(a.dtype, np.integer):
+    raise ValueError('%s must hold integers, got %s' % (what, a.dtype))
+  return a.astype(np.int64)
+
+
+def positives_csr(positives, n_queries, n_gallery, row0=0, nrows=None):
+  """The labels of sim_rank_labelled as validated int32 CSR (offsets [nrows + 1], indices), for the
+  query stripe [row0, row0 + nrows) of n_queries queries against n_gallery gallery rows.  No GPU.
+  `positives` is one of
+    a 1-D integer sequence / array / tensor of length n_queries: one positive per query;
+    a tuple (offsets [n_queries + 1], indices): CSR, query q owns indices[offsets[q]:offsets[q + 1]];
+    a list of n_queries integer sequences: the positives of each query.
+  (Two arrays in a TUPLE are always CSR, per-query lists come in a LIST: two queries are not
+  ambiguous.)  ValueError, naming the query row, for a wrong length, an empty list, an index outside
+  [0, n_gallery) or non-integers."""
+  N, M = int(n_queries), int(n_gallery)
+  if isinstance(positives, tuple):
+    if len(positives) != 2:
+      raise ValueError('positives as a tuple must be (offsets, indices), got %d entries' % len(positives))
+    off = _label_ints(positives[0], 'positives offsets')
+    idx = _label_ints(positives[1], 'positives indices')
+    if off.size != N + 1:
+      raise ValueError('positives offsets have %d entries for %d queries (need %d)' % (off.size, N, N + 1))
+    if off[0] != 0 or off[-1] != idx.size:
+      raise ValueError('positives offsets must run from 0 to len(indices) = %d, got %d .. %d'
+                       % (idx.size, off[0], off[-1]))
+    counts = np.diff(off)
+    if (counts < 0).any():
+      raise ValueError('positives offsets decrease at query row %d' % int(np.flatnonzero(counts < 0)[0]))
+  elif isinstance(positives, list) and any((x.dim() if isinstance(x, torch.Tensor) else np.ndim(x)) > 0
+                                           for x in positives):
+    if len(positives) != N:
+      raise ValueError('positives list %d queries, the query matrix has %d rows' % (len(positives), N))
+    rows = [_label_ints(x, 'the positives of query row %d' % q) for q, x in enumerate(positives)]
+    counts = np.array([r.size for r in rows], dtype=np.int64)
+    off = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum(counts, out=off[1:])
+    idx = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+  else:
+    idx = _label_ints(positives, 'positives')
+    if idx.size != N:
+      raise ValueError('positives hold %d targets, the query matrix has %d rows' % (idx.size, N))
+    counts = np.ones(N, dtype=np.int64)
+    off = np.arange(N + 1, dtype=np.int64)
+  if (counts == 0).any():
+    raise ValueError('query row %d has no positive' % int(np.flatnonzero(counts == 0)[0]))
+  bad = (idx < 0) | (idx >= M)
+  if bad.any():
+    e = int(np.flatnonzero(bad)[0])
+    raise ValueError('query row %d: positive %d lies outside the gallery [0, %d)'
+                     % (int(np.searchsorted(off, e, side='right')) - 1, int(idx[e]), M))
+  if idx.size > 0x7fffffff:
+    raise ValueError('%d (query, positive) pairs do not fit int32' % idx.size)
+  if nrows is None:
+    nrows = N - row0
+  if row0 < 0 or nrows < 0 or row0 + nrows > N:
+    raise ValueError('stripe [%d, %d) outside the %d queries' % (row0, row0 + nrows, N))
+  lo, hi = int(off[row0]), int(off[row0 + nrows])
+  return (off[row0:row0 + nrows + 1] - lo).astype(np.int32), idx[lo:hi].astype(np.int32)
+
+
+def sim_rank_labelled(queries, gallery, positives, row0=0, nrows=None, return_score=False):
+  """Ranks of the stripe [row0, row0+nrows) of queries @ gallery.T against any set of positives per
+  query (cmhse_sim_rank_labelled; `positives`: positives_csr's forms, given for ALL queries — the
+  stripe arguments slice them).  Returns int32 device tensors (rank, top1, best_pos): rank[i] counts
+  the gallery rows that score above query i's best positive (0 = a positive comes first; a negative
+  that ties it exactly is not counted), top1 is sim_rank's, best_pos that best positive (the smallest
+  index on exact ties); with return_score also its float32 score, bit-identical to the same entry of
+  cosine_sim(queries, gallery).  Any gallery size; exact fp32 whatever math_mode() says."""
+  lib = _lib.load()
+  a = _f32c(queries, 'queries')
+  b = _f32c(gallery, 'gallery')
+  N, D = a.shape
+  M = b.shape[0]
+  if b.shape[1] != D:
+    raise ValueError('embedding widths differ')
+  off, idx = positives_csr(positives, N, M, row0, nrows)
+  nrows = off.size - 1
+  out = torch.empty(3, nrows, dtype=torch.int32, device=a.device)
+  score = torch.empty(nrows, dtype=torch.float32, device=a.device) if return_score else None
+  if nrows > 0:
+    labels = np.concatenate([off, idx])          # one upload; the kernels read the device copy
+    labels_d = upload(labels, a.device)
+    ws_bytes = lib.cmhse_sim_rank_labelled_workspace(nrows, idx.size)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    rc = lib.cmhse_sim_rank_labelled(a.data_ptr(), b.data_ptr(), N, M, D, row0, nrows, off.ctypes.data,
+                                     idx.ctypes.data, labels_d.data_ptr(), labels_d.data_ptr() + 4 * off.size,
+                                     idx.size, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                     score.data_ptr() if return_score else None, ws.data_ptr(), ws_bytes,
+                                     _stream())
+    _lib.check(rc, 'cmhse_sim_rank_labelled')
+  return (out[0], out[1], out[2], score) if return_score else (out[0], out[1], out[2])
+
+
 _GROUP_REDUCE = {'max': _lib.GROUP_MAX, 'mean': _lib.GROUP_MEAN}
 
 

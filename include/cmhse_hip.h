@@ -333,6 +333,52 @@ int cmhse_sim_topk(const float* A, const float* B, int32_t N, int32_t M, int32_t
                    int32_t nrows, int32_t K, float* scores /*[nrows,K]*/, int32_t* index /*[nrows,K]*/,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* Labelled ranking (no reference counterpart: the reference's i2t / t2i, and cmhse_sim_rank with them,
+ * can only rank query i against gallery row i).  Queries A [N,D], gallery B [M,D], N and M independent,
+ * d = A B^T in exact fp32 (the MFMA k-chain of every scoring call here, whatever the math mode).  Every
+ * query i of the stripe [row0, row0+nrows) has a non-empty list P_i of positives, gallery rows in
+ * [0, M) (duplicates inside a list are harmless).  With thr[i] = max over p in P_i of d[i,p]:
+ *   rank[i - row0]       = #{ j in [0, M) : d[i,j] > thr[i] }   the 0-based position of the best-placed
+ *                          positive in the descending sort of row i.  Strict, no column excluded: no
+ *                          positive beats thr[i], and a negative that ties it exactly is not counted
+ *                          (the optimistic tie rule of cmhse_sim_rank);
+ *   top1[i - row0]       = argmax_j d[i,j], smallest j on exact ties (as cmhse_sim_rank);
+ *   best_pos[i - row0]   = the p in P_i with d[i,p] == thr[i], the smallest such p on exact ties (the
+ *                          64-bit key of cmhse_sim_topk: independent of tiling and scheduling);
+ *   best_score[i - row0] = the bits of d[i, best_pos] as the kernel computed them, never recomputed
+ *                          (may be NULL).
+ * With M >= N and P_i = {i}, rank and top1 equal cmhse_sim_rank's bit for bit.  Query stripes (their
+ * labels sliced with them) concatenate bit for bit into the whole call.
+ *
+ * Labels are CSR relative to the stripe: pos_off[nrows+1] (0 first, strictly increasing: every query
+ * has a positive; pos_off[nrows] == n_pairs) and pos_idx[n_pairs]; query row0 + q owns
+ * pos_idx[pos_off[q] .. pos_off[q+1]).  Both arrays are passed twice, as cmhse_group_scores takes its
+ * plan: the host copies are validated in full (O(n_pairs)) before anything is launched, the kernels
+ * read the device copies, which must hold the same values.
+ *
+ * Returns CMHSE_ERR_ARG, before anything is launched, for: a null A / B / label / output pointer
+ * (best_score excepted); N, M or D <= 0; a stripe outside [0, N]; n_pairs < nrows; pos_off_host[0] != 0,
+ * a prefix sum that does not increase (an empty list), pos_off_host[nrows] != n_pairs; an index outside
+ * [0, M).  CMHSE_ERR_WORKSPACE: workspace unaligned (256 bytes) or smaller than
+ * cmhse_sim_rank_labelled_workspace(nrows, n_pairs) (0 for nrows <= 0 or n_pairs < nrows; otherwise
+ * nrows thresholds and 2 x nrows keys — it does not grow with n_pairs).  nrows == 0 (with n_pairs == 0):
+ * nothing is launched and every pointer but A and B may be NULL.
+ *
+ * Cost: a threshold pass of ceil(n_pairs / 128) tiles of 128 x 128 x D (the pairs in CSR order, operand
+ * A row r = the query of pair r, operand B row c = the gallery row of pair c; the tile's diagonal holds
+ * the pairs' scores, each folded into its query's key by a 64-bit atomic max), a launch that decodes
+ * the keys, the counting pass of ceil(nrows / 128) x ceil(M / 128) tiles that cmhse_sim_rank runs (one
+ * compare term fewer) and its top-1 pass.  With one positive per query that is cmhse_sim_rank's tile
+ * work plus one small launch; the thresholds come out of the same MFMA chain as the scores they are
+ * compared with, which is what makes the strict compare exact.  Inputs are assumed finite. */
+size_t cmhse_sim_rank_labelled_workspace(int32_t nrows, int32_t n_pairs);
+int cmhse_sim_rank_labelled(const float* A, const float* B, int32_t N, int32_t M, int32_t D, int32_t row0,
+                            int32_t nrows, const int32_t* pos_off_host, const int32_t* pos_idx_host,
+                            const int32_t* pos_off, const int32_t* pos_idx, int32_t n_pairs,
+                            int32_t* rank /*[nrows]*/, int32_t* top1 /*[nrows]*/,
+                            int32_t* best_pos /*[nrows]*/, float* best_score /*[nrows] or NULL*/,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* Group-wise video <-> paragraph scores and ranking from the low-level rows (the score
  * GroupWiseContrastiveLoss trains on, loss.py:26-41; upstream's validate() has its evaluation
  * commented out, train.py:228-244).  clips [Nc, D] and caps [Ns, D] are encode_data's clip and
