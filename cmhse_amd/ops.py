@@ -1515,6 +1515,8 @@ def groupwise_fwd(im, s, num_clips, num_caps, margin, max_violation, norm):
   B = len(num_clips)
   if len(num_caps) != B or sum(num_clips) != n or sum(num_caps) != s.shape[0] or s.shape[0] != n:
     raise ValueError('GroupWiseContrastiveLoss: block sizes must tile the rows (loss.py:33)')
+  if B == 0 or min(num_clips) <= 0 or min(num_caps) <= 0:     # an empty block has no max and no mean
+    raise ValueError('GroupWiseContrastiveLoss: every video needs at least one clip and one caption')
   off = np.zeros(2 * (B + 1), dtype=np.int32)
   np.cumsum(np.asarray(num_clips), out=off[1:B + 1])
   np.cumsum(np.asarray(num_caps), out=off[B + 2:])

@@ -216,6 +216,10 @@ def test_python_wrappers_validate_shapes(dev):
     ops.sim_rank(a, torch.randn(4, 9, device=dev))
   with pytest.raises(ValueError):
     GroupWiseContrastiveLoss(margin=0.2)(a, a, [2, 1], [2, 2])
+  with pytest.raises(ValueError):
+    GroupWiseContrastiveLoss(margin=0.2)(a, a, [4, 0], [2, 2])     # a video without clips: empty blocks
+  with pytest.raises(ValueError):
+    ops.groupwise_fwd(a, a, [2, 2], [0, 4], 0.2, True, True)
   with pytest.raises(NotImplementedError):
     ContrastiveLoss(margin=0.2, measure='order')
 

@@ -7,7 +7,9 @@
   python tools/mutation_check.py run [name ...]     (GPU box)
       runs the selected GPU tests once per mutant with CMHSE_HIP_LIB pointing at it and reports
       which tests FAILED — a mutant that no test kills is a hole in the suite.  Also runs the same
-      selection on the product library (must pass).
+      selection on the product library (must pass).  `--tests <pytest arguments>` after the names
+      replaces the selection, e.g. to show that a mutant survives the tests that were there before
+      the ones written to kill it.
 
 Mutants:
   attn_eps_fwd   gru_attention.hpp: the masked softmax's `+ 0.0001f` (layers.py:158-162) -> `+ 0.0f`
@@ -19,6 +21,10 @@ Mutants:
   fwd_tail_two_blocks, mid_combine_4_waves, tiny_all_prev_state, tile_all_prev_state, scalar_k_remainder
                  the forward step shapes (killed by tests/test_gpu_fwd_shapes.py; the tail one by
                  test_gpu_chain.py's forward resident-tail test)
+  gw_reduce_first_trip, gw_argmax_last_tie, gw_expand_mean_by_width, gw_expand_first_trip, euclid_norm_by_cols
+                 the loss kernels at training shapes (killed by tests/test_gpu_loss_shapes.py; of the four
+                 group-wise ones only the mean by width is caught by an older test:
+                 profiles/loss_shapes_mutation_check.txt)
 """
 import os
 import shutil
@@ -43,7 +49,8 @@ MUTANTS = {
     'gru_bhn_outside_r_tiled': ('gru_step_tile.hpp', 'const float ng = tanhf_(acc[ms][2][r] + b_in + rg * ghn);',
                                 'const float ng = tanhf_(acc[ms][2][r] + b_in + rg * acc[ms][3][r] + b_hn);'),
     # evaluation.py:92-95 / 131-134 via the documented tie rule: strict '>' for the rank
-    'rank_counts_ties': ('sim.hip', 'valid && j != gi && v > dii', 'valid && j != gi && v >= dii'),
+    'rank_counts_ties': ('sim.hip', 'valid && (MODE == kSimLabel || j != gi) && v > dii',
+                         'valid && (MODE == kSimLabel || j != gi) && v >= dii'),
     # loss.py:100-103: the diagonal of both cost matrices is masked to zero
     'loss_diag_not_masked': ('sim.hip', 'if (j == i) c = 0.f;', ''),
     # loss.py:106-111: max_violation keeps the hardest negative per row / column only
@@ -78,13 +85,28 @@ MUTANTS = {
     # the scalar-load tile loops keep the 4th element of a k group past K (its load is clamped to the
     # row's last element, so the value is that element instead of 0)
     'scalar_k_remainder': ('nt_core.hpp', 'v.w = (valid && k + 3 < klim) ? v.w : 0.f;', 'v.w = valid ? v.w : 0.f;'),
+    # loss kernels at training shapes (tests/test_gpu_loss_shapes.py): value-only edits as above.
+    # block_reduce_kernel visits a thread's first element only: wrong for blocks of more than 256 elements
+    'gw_reduce_first_trip': ('sim.hip', 'for (int e = tid; e < cnt; e += kThreads) {', 'if (int e = tid; e < cnt) {'),
+    # ... its per-thread scan keeps the LAST of a thread's tied maxima (loss.py:31 torch.max: the first)
+    'gw_argmax_last_tie': ('sim.hip', 'if (v > best || (v == best && flat < arg)) {',
+                           'if (v > best || (v == best && flat > arg)) {'),
+    # the block mean's gradient divides by the block's width instead of its element count
+    'gw_expand_mean_by_width': ('bwd_loss_kernels.hpp', 'g / static_cast<float>(cnt);', 'g / static_cast<float>(w);'),
+    # groupwise_expand_kernel writes a thread's first element only
+    'gw_expand_first_trip': ('bwd_loss_kernels.hpp', 'for (int e = threadIdx.x; e < cnt; e += kThreads) {',
+                             'if (int e = threadIdx.x; e < cnt) {'),
+    # decoder/loss.py:24: the mean is over the rows
+    'euclid_norm_by_cols': ('bwd_loss_kernels.hpp', 'if (q.norm) sc /= static_cast<float>(q.rows);',
+                            'if (q.norm) sc /= static_cast<float>(q.cols);'),
 }
 # the tests that must kill them (and pass on the product library)
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
-          'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py', '-k',
+          'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py',
+          'tests/test_gpu_loss_shapes.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
           'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
-          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail']
+          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes']
 
 
 def build(only=()):
@@ -113,13 +135,18 @@ def build(only=()):
 
 
 def run(only=()):
+  only = list(only)
+  select = SELECT
+  if '--tests' in only:
+    select = only[only.index('--tests') + 1:]
+    only = only[:only.index('--tests')]
   results = {}
   for name in [None] + sorted(m for m in MUTANTS if not only or m in only):
     env = dict(os.environ)
     if name:
       env['CMHSE_HIP_LIB'] = os.path.join(OUT, 'libcmhse_%s.so' % name)
     res = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-m', 'gpu', '-p', 'no:cacheprovider',
-                          '--tb=line'] + SELECT, cwd=REPO, env=env, stdout=subprocess.PIPE,
+                          '--tb=line'] + select, cwd=REPO, env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.STDOUT, text=True)
     failed = [l for l in res.stdout.splitlines() if l.startswith('FAILED')]
     errors = [l for l in res.stdout.splitlines() if l.startswith('ERROR')]
