@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libcmhse_hip.so')
-SOURCES = ['gru.hip', 'sim.hip', 'bwd.hip', 'topk.hip', 'group.hip']
+SOURCES = ['gru.hip', 'sim.hip', 'bwd.hip', 'loss.hip', 'topk.hip', 'group.hip']
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hpp')) + \
     [os.path.join(os.path.dirname(HERE), 'include', 'cmhse_hip.h')]
 

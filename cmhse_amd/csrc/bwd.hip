@@ -1,6 +1,6 @@
-// bwd.hip — backward pass of the hot path: what `loss.backward()`
-// (/root/reference/model.py:367) computes through layers.{Seq2Seq,Attention,Maxout}.forward,
-// F.normalize and ContrastiveLoss.forward, as hand-written gfx950 kernels.
+// bwd.hip — backward pass of the encoders: what `loss.backward()`
+// (/root/reference/model.py:367) computes through layers.{Seq2Seq,Attention,Maxout}.forward, as
+// hand-written gfx950 kernels.  (The backward of F.normalize and of the losses is loss.hip's.)
 //
 //   cmhse_gru_pool_bwd      pooling backward -> dpool[sumT,H]; BPTT over the packed steps in reverse
 //                           (dh_{t} = dgates_{t+1} . W_hh + carry and the gate derivatives: one
@@ -8,8 +8,6 @@
 //                           sizes); weight gradients straight from the packed rows in chunks of
 //                           time steps beside the chain (tn_rows.hpp); optional d(input) / d(h0) /
 //                           d(embedding table).
-//   cmhse_l2norm_rows_bwd   F.normalize backward.
-//   cmhse_contrastive_bwd   d loss / d im, d loss / d s from the stored score matrix.
 //
 // Determinism: every reduction runs in a fixed order except the sums into the embedding table and
 // into a time-constant decoder input (float atomics, like torch's CUDA embedding backward).
@@ -23,11 +21,9 @@
 #include "nt_core.hpp"
 #include "tn_core.hpp"
 #include "tn_rows.hpp"
-#include "step_loss.hpp"
 
 #include "bwd_pool_kernels.hpp"
 #include "bwd_step_kernels.hpp"
-#include "bwd_loss_kernels.hpp"
 
 namespace cmhse {
 
@@ -46,21 +42,6 @@ static void launch_colsum(const float* in, const float* w, float* out, float* sc
                      in, w, scratch, rows, cols, ld);
   hipLaunchKernelGGL(colsum_final_kernel, dim3((cols + kThreads - 1) / kThreads), dim3(kThreads),
                      0, st, scratch, out, slabs, cols);
-}
-
-static void launch_tn(const float* a, int64_t lda, const float* b, int64_t ldb,
-                      const uint64_t* b_addr, float* c, int64_t ldc, int M, int N, int64_t K,
-                      const float* scale, bool vec, hipStream_t st) {
-  TnParams q;
-  q.a = a; q.lda = lda; q.b = b; q.ldb = ldb; q.b_addr = b_addr; q.c = c; q.ldc = ldc;
-  q.M = M; q.N = N; q.K = K; q.n_tiles = (N + 127) / 128; q.scale = scale;
-  q.blk_off = nullptr; q.blk_stride = 0;
-  const unsigned grid = static_cast<unsigned>(q.n_tiles) * ((M + 127) / 128);
-  const size_t smem = TnSmem<128, 128>::kBytes;
-  if (vec)
-    hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(grid), dim3(kThreads), smem, st, q);
-  else
-    hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(grid), dim3(kThreads), smem, st, q);
 }
 
 // Split-K for products with few output tiles and a long K: the workgroups of one tile accumulate
@@ -746,315 +727,4 @@ extern "C" int cmhse_gru_pool_bwd(const cmhse_seq_batch* b, const cmhse_gru_weig
   r.stream = nullptr;
   r.side_stream = nullptr;
   return cmhse_gru_pool_bwd_multi(&r, 1, stream_);
-}
-
-extern "C" int cmhse_l2norm_rows_bwd(const float* x, const float* g, float* dx, int32_t rows,
-                                     int32_t cols, void* stream_) {
-  if (!x || !g || !dx || rows < 0 || cols <= 0) return CMHSE_ERR_ARG;
-  if (rows == 0) return CMHSE_OK;
-  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(rows), dim3(kThreads), 0,
-                     static_cast<hipStream_t>(stream_), x, g, dx, cols);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-extern "C" size_t cmhse_contrastive_bwd_workspace(int32_t n) {
-  if (n <= 0) return 0;
-  return 2 * ws_align(static_cast<size_t>(n) * n * 4) + 4 * ws_align(static_cast<size_t>(n) * 4);
-}
-
-extern "C" int cmhse_contrastive_bwd(const float* im, const float* s, const float* scores,
-                                     int32_t n, int32_t D, float margin, int32_t max_violation,
-                                     int32_t norm, const float* grad_out, float* d_im, float* d_s,
-                                     void* workspace, size_t workspace_bytes, void* stream_) {
-  if (!im || !s || !scores || !grad_out || !d_im || !d_s || !workspace || n <= 0 || D <= 0)
-    return CMHSE_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
-      workspace_bytes < cmhse_contrastive_bwd_workspace(n))
-    return CMHSE_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  const size_t mat = ws_align(static_cast<size_t>(n) * n * 4), vecb = ws_align(static_cast<size_t>(n) * 4);
-  LossBwdParams q;
-  q.scores = scores; q.gout = grad_out; q.n = n; q.max_violation = max_violation; q.norm = norm;
-  q.margin = margin;
-  q.G = reinterpret_cast<float*>(ws);
-  q.GT = reinterpret_cast<float*>(ws + mat);
-  q.row_arg = reinterpret_cast<int32_t*>(ws + 2 * mat);
-  q.col_arg = reinterpret_cast<int32_t*>(ws + 2 * mat + vecb);
-  q.row_cnt = reinterpret_cast<float*>(ws + 2 * mat + 2 * vecb);
-  q.col_cnt = reinterpret_cast<float*>(ws + 2 * mat + 3 * vecb);
-  q.blk_off = nullptr; q.blk_stride = 0; q.score_stride = 0; q.vec_stride = 0;
-  hipLaunchKernelGGL(loss_bwd_stats_kernel, dim3((2 * n + 3) / 4), dim3(kThreads), 0, st, q);
-  const int64_t elems = static_cast<int64_t>(n) * n;
-  hipLaunchKernelGGL(loss_bwd_build_kernel, dim3(static_cast<unsigned>((elems + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, st, q);
-  const bool vec = (n % 4 == 0) && (D % 4 == 0);
-  // d im[i][d] = sum_j G[i][j] s[j][d]  = TN(A = G^T, B = s);  d s[j][d] = sum_i G[i][j] im[i][d]
-  launch_tn(q.GT, n, s, D, nullptr, d_im, D, n, D, n, nullptr, vec, st);
-  launch_tn(q.G, n, im, D, nullptr, d_s, D, n, D, n, nullptr, vec, st);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-extern "C" size_t cmhse_contrastive_blocks_bwd_workspace(int32_t n_blocks, int32_t max_n) {
-  if (n_blocks <= 0 || max_n <= 0) return 0;
-  return static_cast<size_t>(n_blocks) *
-         (2 * ws_align(static_cast<size_t>(max_n) * max_n * 4) + 4 * ws_align(static_cast<size_t>(max_n) * 4));
-}
-
-extern "C" int cmhse_contrastive_blocks_bwd(const float* im, const float* s, const float* scores,
-                                            const int32_t* blk_off, int32_t n_blocks, int32_t max_n,
-                                            int32_t D, float margin, int32_t max_violation,
-                                            int32_t norm, const float* grad_out, float* d_im,
-                                            float* d_s, void* workspace, size_t workspace_bytes,
-                                            void* stream_) {
-  if (!im || !s || !scores || !blk_off || !grad_out || !d_im || !d_s || !workspace || n_blocks <= 0 ||
-      max_n <= 0 || D <= 0)
-    return CMHSE_ERR_ARG;
-  if (n_blocks > 65535) return CMHSE_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
-      workspace_bytes < cmhse_contrastive_blocks_bwd_workspace(n_blocks, max_n))
-    return CMHSE_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  const size_t mat = ws_align(static_cast<size_t>(max_n) * max_n * 4);
-  const size_t vecb = ws_align(static_cast<size_t>(max_n) * 4);
-  LossBwdParams q;
-  q.scores = scores; q.gout = grad_out; q.n = max_n; q.max_violation = max_violation; q.norm = norm;
-  q.margin = margin;
-  q.G = reinterpret_cast<float*>(ws);
-  q.GT = reinterpret_cast<float*>(ws + n_blocks * mat);
-  char* vecs = ws + 2 * n_blocks * mat;
-  q.row_arg = reinterpret_cast<int32_t*>(vecs);
-  q.col_arg = reinterpret_cast<int32_t*>(vecs + n_blocks * vecb);
-  q.row_cnt = reinterpret_cast<float*>(vecs + 2 * n_blocks * vecb);
-  q.col_cnt = reinterpret_cast<float*>(vecs + 3 * n_blocks * vecb);
-  q.blk_off = blk_off;
-  q.blk_stride = static_cast<int64_t>(mat / 4);           // floats between blocks of G / GT
-  q.vec_stride = static_cast<int32_t>(vecb / 4);
-  // the stored scores of the forward pass: block b at scores + b * max_n * max_n
-  // (cmhse_contrastive_blocks_fwd's workspace), leading dimension = the block's own n
-  q.score_stride = static_cast<int64_t>(max_n) * max_n;
-  hipLaunchKernelGGL(loss_bwd_stats_kernel, dim3((2 * max_n + 3) / 4, n_blocks), dim3(kThreads), 0, st, q);
-  const int64_t elems = static_cast<int64_t>(max_n) * max_n;
-  hipLaunchKernelGGL(loss_bwd_build_kernel,
-                     dim3(static_cast<unsigned>((elems + kThreads - 1) / kThreads), n_blocks),
-                     dim3(kThreads), 0, st, q);
-  // d im[i][d] = sum_j G[i][j] s[j][d] = TN(A = G^T, B = s);  d s[j][d] = sum_i G[i][j] im[i][d]
-  TnParams t;
-  t.lda = max_n; t.ldb = D; t.b_addr = nullptr; t.ldc = D; t.M = max_n; t.N = D; t.K = max_n;
-  t.n_tiles = (D + 127) / 128; t.scale = nullptr; t.blk_off = blk_off; t.blk_stride = q.blk_stride;
-  const unsigned grid = static_cast<unsigned>(t.n_tiles) * ((max_n + 127) / 128);
-  const size_t smem = TnSmem<128, 128>::kBytes;
-  t.a = q.GT; t.b = s; t.c = d_im;
-  hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(grid, n_blocks), dim3(kThreads), smem, st, t);
-  t.a = q.G; t.b = im; t.c = d_s;
-  hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(grid, n_blocks), dim3(kThreads), smem, st, t);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-// ---------------------------------------------------------------------------------------------
-// cmhse_step_losses_bwd: per-term upstream gradients, the batched ContrastiveLoss backward, then
-// F.normalize's backward over the sum of every use of each encoder output.
-// ---------------------------------------------------------------------------------------------
-struct StepNormBwdParams {
-  const float* x[CMHSE_STEP_LOSS_MAX];
-  float* dx[CMHSE_STEP_LOSS_MAX];
-  int32_t rows[CMHSE_STEP_LOSS_MAX];
-  int32_t term_a[CMHSE_STEP_LOSS_MAX], term_b[CMHSE_STEP_LOSS_MAX], term_off[CMHSE_STEP_LOSS_MAX];
-  float weight[CMHSE_STEP_LOSS_MAX];
-  int32_t n_emb, n_terms, D;
-  const float* d_im;  // [R, D]
-  const float* d_s;   // [R, D]
-};
-
-__global__ void step_gout_kernel(const StepNormBwdParams p, const float* grad_total, float* gout) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const float g = *grad_total;
-#pragma unroll
-    for (int k = 0; k < CMHSE_STEP_LOSS_MAX; ++k)
-      if (k < p.n_terms) gout[k] = p.weight[k] * g;
-  }
-}
-
-// one workgroup per encoder-output row: g = sum over the terms that use the row (term order, left
-// operand before right), then l2norm_bwd_kernel's arithmetic
-__global__ __launch_bounds__(kThreads) void step_norm_bwd_kernel(const StepNormBwdParams p) {
-  int e = -1, i = 0, off = 0;
-  const float* xr = nullptr;
-  float* dxr = nullptr;
-#pragma unroll
-  for (int k = 0; k < CMHSE_STEP_LOSS_MAX; ++k) {
-    if (k < p.n_emb) {
-      const int r = static_cast<int>(blockIdx.x) - off;
-      if (r >= 0 && r < p.rows[k]) {
-        e = k;
-        i = r;
-        xr = p.x[k] + static_cast<int64_t>(r) * p.D;
-        dxr = p.dx[k] + static_cast<int64_t>(r) * p.D;
-      }
-      off += p.rows[k];
-    }
-  }
-  if (e < 0) return;
-  const float* use[2 * CMHSE_STEP_LOSS_MAX];
-#pragma unroll
-  for (int k = 0; k < CMHSE_STEP_LOSS_MAX; ++k) {
-    const bool live = k < p.n_terms;
-    const int64_t row = static_cast<int64_t>(p.term_off[k] + i) * p.D;
-    use[2 * k] = (live && p.term_a[k] == e) ? p.d_im + row : nullptr;
-    use[2 * k + 1] = (live && p.term_b[k] == e) ? p.d_s + row : nullptr;
-  }
-  auto grad = [&](int c) {
-    float g = 0.f;
-#pragma unroll
-    for (int u = 0; u < 2 * CMHSE_STEP_LOSS_MAX; ++u)
-      if (use[u] != nullptr) g += use[u][c];
-    return g;
-  };
-  float ss = 0.f, sg = 0.f;
-  for (int c = threadIdx.x; c < p.D; c += kThreads) {
-    ss += xr[c] * xr[c];
-    sg += xr[c] * grad(c);
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    ss += __shfl_xor(ss, o, 64);
-    sg += __shfl_xor(sg, o, 64);
-  }
-  __shared__ float p1[4], p2[4];
-  __shared__ float s_inv, s_dot;
-  if ((threadIdx.x & 63) == 0) {
-    p1[threadIdx.x >> 6] = ss;
-    p2[threadIdx.x >> 6] = sg;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float n2 = p1[0] + p1[1] + p1[2] + p1[3];
-    const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-    s_inv = inv;
-    s_dot = (p2[0] + p2[1] + p2[2] + p2[3]) * inv * inv;
-  }
-  __syncthreads();
-  const float inv = s_inv, d = s_dot;
-  for (int c = threadIdx.x; c < p.D; c += kThreads) dxr[c] = (grad(c) - xr[c] * d) * inv;
-}
-
-extern "C" int cmhse_step_losses_bwd(const cmhse_step_losses* d, const float* grad_total,
-                                     float* const* dx, void* workspace, size_t workspace_bytes,
-                                     void* stream_) {
-  StepLossLayout L;
-  if (!grad_total || !dx || !workspace || !step_loss_layout(d, &L)) return CMHSE_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 || workspace_bytes < L.bytes)
-    return CMHSE_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  StepNormBwdParams p = {};
-  int64_t total_rows = 0;
-  for (int e = 0; e < d->n_emb; ++e) {
-    if (!d->x[e] || !dx[e]) return CMHSE_ERR_ARG;
-    p.x[e] = d->x[e];
-    p.dx[e] = dx[e];
-    p.rows[e] = d->rows[e];
-    total_rows += d->rows[e];
-  }
-  if (total_rows > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
-  int32_t off = 0;
-  for (int k = 0; k < d->n_terms; ++k) {
-    p.term_a[k] = d->term_a[k];
-    p.term_b[k] = d->term_b[k];
-    p.term_off[k] = off;
-    p.weight[k] = d->weight[k];
-    off += d->rows[d->term_a[k]];
-  }
-  p.n_emb = d->n_emb;
-  p.n_terms = d->n_terms;
-  p.D = d->D;
-  float* d_im = reinterpret_cast<float*>(ws + L.d_im);
-  float* d_s = reinterpret_cast<float*>(ws + L.d_s);
-  p.d_im = d_im;
-  p.d_s = d_s;
-  float* gout = reinterpret_cast<float*>(ws + L.gout);
-  hipLaunchKernelGGL(step_gout_kernel, dim3(1), dim3(64), 0, st, p, grad_total, gout);
-  const int rc = cmhse_contrastive_blocks_bwd(
-      reinterpret_cast<const float*>(ws + L.y_im), reinterpret_cast<const float*>(ws + L.y_s),
-      reinterpret_cast<const float*>(ws + L.fwd_ws), reinterpret_cast<const int32_t*>(ws + L.blk_off),
-      d->n_terms, L.max_n, d->D, d->margin, d->max_violation, d->norm, gout, d_im, d_s,
-      ws + L.bwd_ws, cmhse_contrastive_blocks_bwd_workspace(d->n_terms, L.max_n), stream_);
-  if (rc != CMHSE_OK) return rc;
-  hipLaunchKernelGGL(step_norm_bwd_kernel, dim3(static_cast<unsigned>(total_rows)), dim3(kThreads), 0,
-                     st, p);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-extern "C" int cmhse_euclid_fwd(const float* a, const float* b, const uint64_t* b_rows, int32_t rows,
-                                int32_t cols, int32_t norm, float* loss, float* row_dist,
-                                void* stream_) {
-  if (!a || (!b && !b_rows) || !loss || !row_dist || rows <= 0 || cols <= 0) return CMHSE_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  EuclidParams q;
-  q.a = a; q.b = b; q.b_rows = b_rows; q.dist = row_dist; q.d_a = nullptr; q.gout = nullptr;
-  q.loss = loss; q.rows = rows; q.cols = cols; q.norm = norm;
-  hipLaunchKernelGGL(euclid_rows_kernel, dim3(rows), dim3(kThreads), 0, st, q, 0);
-  hipLaunchKernelGGL(euclid_final_kernel, dim3(1), dim3(kThreads), 0, st, q);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-extern "C" int cmhse_euclid_bwd(const float* a, const float* b, const uint64_t* b_rows, int32_t rows,
-                                int32_t cols, int32_t norm, const float* grad_out, float* d_a,
-                                void* stream_) {
-  if (!a || (!b && !b_rows) || !grad_out || !d_a || rows <= 0 || cols <= 0) return CMHSE_ERR_ARG;
-  EuclidParams q;
-  q.a = a; q.b = b; q.b_rows = b_rows; q.dist = nullptr; q.d_a = d_a; q.gout = grad_out;
-  q.loss = nullptr; q.rows = rows; q.cols = cols; q.norm = norm;
-  hipLaunchKernelGGL(euclid_rows_kernel, dim3(rows), dim3(kThreads), 0,
-                     static_cast<hipStream_t>(stream_), q, 1);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-extern "C" size_t cmhse_groupwise_bwd_workspace(int32_t n, int32_t B) {
-  if (n <= 0 || B <= 0) return 0;
-  return 2 * ws_align(static_cast<size_t>(n) * n * 4) + cmhse_contrastive_bwd_workspace(B);
-}
-
-extern "C" int cmhse_groupwise_bwd(const float* im, const float* s, int32_t n, int32_t D,
-                                   const int32_t* row_off, const int32_t* col_off, int32_t B,
-                                   float margin, int32_t max_violation, int32_t norm,
-                                   const float* reduced, const int32_t* arg, const float* grad_out,
-                                   float* d_im, float* d_s, void* workspace,
-                                   size_t workspace_bytes, void* stream_) {
-  if (!im || !s || !row_off || !col_off || !reduced || !arg || !grad_out || !d_im || !d_s ||
-      !workspace || n <= 0 || D <= 0 || B <= 0 || B > 65535)
-    return CMHSE_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
-      workspace_bytes < cmhse_groupwise_bwd_workspace(n, B))
-    return CMHSE_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  const size_t big = ws_align(static_cast<size_t>(n) * n * 4);
-  float* dS = reinterpret_cast<float*>(ws);
-  float* dST = reinterpret_cast<float*>(ws + big);
-  char* lws = ws + 2 * big;
-  const size_t mat = ws_align(static_cast<size_t>(B) * B * 4), vecb = ws_align(static_cast<size_t>(B) * 4);
-  LossBwdParams q;
-  q.scores = reduced; q.gout = grad_out; q.n = B; q.max_violation = max_violation; q.norm = norm;
-  q.margin = margin;
-  q.G = reinterpret_cast<float*>(lws);
-  q.GT = reinterpret_cast<float*>(lws + mat);
-  q.row_arg = reinterpret_cast<int32_t*>(lws + 2 * mat);
-  q.col_arg = reinterpret_cast<int32_t*>(lws + 2 * mat + vecb);
-  q.row_cnt = reinterpret_cast<float*>(lws + 2 * mat + 2 * vecb);
-  q.col_cnt = reinterpret_cast<float*>(lws + 2 * mat + 3 * vecb);
-  q.blk_off = nullptr; q.blk_stride = 0; q.score_stride = 0; q.vec_stride = 0;
-  hipLaunchKernelGGL(loss_bwd_stats_kernel, dim3((2 * B + 3) / 4), dim3(kThreads), 0, st, q);
-  const int64_t elems = static_cast<int64_t>(B) * B;
-  hipLaunchKernelGGL(loss_bwd_build_kernel, dim3(static_cast<unsigned>((elems + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, st, q);
-  ExpandParams ep;
-  ep.g_red = q.G; ep.arg = arg; ep.row_off = row_off; ep.col_off = col_off; ep.dS = dS;
-  ep.dST = dST; ep.n = n; ep.B = B; ep.use_max = max_violation;
-  hipLaunchKernelGGL(groupwise_expand_kernel, dim3(B, B), dim3(kThreads), 0, st, ep);
-  const bool vec = (n % 4 == 0) && (D % 4 == 0);
-  launch_tn(dST, n, s, D, nullptr, d_im, D, n, D, n, nullptr, vec, st);
-  launch_tn(dS, n, im, D, nullptr, d_s, D, n, D, n, nullptr, vec, st);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }

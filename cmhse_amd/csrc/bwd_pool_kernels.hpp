@@ -2,7 +2,7 @@
 //
 // Backward of the pooling and the small helpers around the BPTT: transposes, column sums, the packed-row address
 // tables, max / last pooling scatter, attention-pool backward (the +1e-4 of layers.py:158-162 is in its
-// denominator too), and the plain TN / NT products of the attention projection's gradients.  Included by bwd.hip only.
+// denominator too), and the plain NT product of the attention projection's gradients.  Included by bwd.hip only.
 #pragma once
 
 namespace cmhse {
@@ -230,61 +230,6 @@ __global__ __launch_bounds__(kThreads) void attn_du_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------
 // generic GEMM kernels
 // ---------------------------------------------------------------------------------------------
-struct TnParams {
-  const float* a;  // [K, lda], columns m
-  int64_t lda;
-  const float* b;  // [K, ldb] or rows through b_addr
-  int64_t ldb;
-  const uint64_t* b_addr;
-  float* c;  // [M, ldc]
-  int64_t ldc;
-  int32_t M, N, n_tiles;
-  int64_t K;
-  const float* scale;  // optional device scalar multiplied into C
-  // several products in one launch (blockIdx.y = block b, rows blk_off[b] .. blk_off[b+1] of the
-  // caller's row-blocked operands): A is the block's [n_b, n_b] matrix at a + b * blk_stride
-  // (lda = n_b), B / C are rows blk_off[b].. of b / c; M = K = n_b
-  const int32_t* blk_off;
-  int64_t blk_stride;
-};
-
-template <bool VEC>
-__global__ __launch_bounds__(kThreads) void gemm_tn_kernel(const TnParams q_) {
-  TnParams q = q_;
-  if (q.blk_off != nullptr) {
-    const int b = blockIdx.y, off = q.blk_off[b], nb = q.blk_off[b + 1] - off;
-    q.a += b * q.blk_stride;
-    q.lda = nb;
-    q.b += static_cast<int64_t>(off) * q.ldb;
-    q.c += static_cast<int64_t>(off) * q.ldc;
-    q.M = nb;
-    q.K = nb;
-    if ((blockIdx.x / q.n_tiles) * 128 >= nb) return;   // M tile outside this (smaller) block
-  }
-  constexpr int BM = 128, BN = 128;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int n0 = (blockIdx.x % q.n_tiles) * BN, m0 = (blockIdx.x / q.n_tiles) * BM;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = zero16();
-  tn_mainloop<BM, BN, VEC>(smem, q.a, q.lda, q.M, q.b, q.ldb, q.b_addr, q.N, q.K, m0, n0, acc);
-  const float sc = q.scale ? *q.scale : 1.0f;
-#pragma unroll
-  for (int ms = 0; ms < 2; ++ms)
-#pragma unroll
-    for (int ns = 0; ns < 2; ++ns)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 64 + ms * 32 + acc_row(r, lane);
-        const int n = n0 + wn * 64 + ns * 32 + acc_col(lane);
-        if (m < q.M && n < q.N) q.c[static_cast<int64_t>(m) * q.ldc + n] = sc * acc[ms][ns][r];
-      }
-}
-
 // C[m][n] = sum_k A[m][k] B[n][k]; output row m goes to c_addr[m] (or c + m*ldc);
 // mode 0 store, 1 accumulate (+=), 2 atomic add (rows may repeat: embedding-table scatter),
 // 3 store the partial product of K segment blockIdx.y at c + blockIdx.y * M * ldc (dense scratch;

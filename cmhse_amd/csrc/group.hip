@@ -4,7 +4,7 @@
 // c of paragraph j: the block maximum (CMHSE_GROUP_MAX) or the block mean (CMHSE_GROUP_MEAN: the
 // fp32 scores summed in fp64 sequentially in row-major order — clip-major, then caption — divided in
 // fp64 by the count, rounded to fp32).  That is the block reduction of GroupWiseContrastiveLoss
-// (loss.py:26-41, sim.hip: block_reduce_kernel, which adds in exactly this order for blocks of at most
+// (loss.py:26-41, loss_kernels.hpp: block_reduce_kernel, which adds in exactly this order for blocks of at most
 // 256 entries), evaluated on the whole validation split without the Nc x Ns clip x caption matrix.
 //
 //   cmhse_group_plan    host only: packs WHOLE videos into row tiles of at most 128 clip rows and

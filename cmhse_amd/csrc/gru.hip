@@ -38,6 +38,7 @@
 #include "gru_ws.hpp"
 #include "grid_sync.hpp"
 #include "nt_core.hpp"
+#include "norm_rows.hpp"
 
 #include "gru_step_tile.hpp"
 #include "gru_attention.hpp"

@@ -14,27 +14,7 @@ __global__ __launch_bounds__(kThreads) void l2norm_rows_kernel(const float* __re
                                                                float* __restrict__ y, int cols,
                                                                int64_t ld) {
   const int64_t row = blockIdx.x;
-  const float* xr = x + row * ld;
-  float* yr = y + row * ld;
-  float ss = 0.f;
-  for (int c = threadIdx.x; c < cols; c += kThreads) {
-    const float v = xr[c];
-    ss += v * v;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
-  __shared__ float s_part[kThreads / 64];
-  __shared__ float s_inv;
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = ss;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int i = 0; i < kThreads / 64; ++i) t += s_part[i];
-    s_inv = 1.0f / fmaxf(sqrtf(t), 1e-12f);
-  }
-  __syncthreads();
-  const float inv = s_inv;
-  for (int c = threadIdx.x; c < cols; c += kThreads) yr[c] = xr[c] * inv;
+  l2norm_row(x + row * ld, y + row * ld, cols);   // norm_rows.hpp
 }
 
 // nn.Embedding lookup as a plain row gather (only used when the caller asks for the word tensor,

@@ -1,4 +1,4 @@
-// sim.hip — N x M cosine-similarity contraction with fused ranking / loss epilogues.
+// sim.hip — N x M cosine-similarity contraction with fused ranking epilogues.
 //
 //   cmhse_sim_rank        evaluation.i2t / t2i  (/root/reference/evaluation.py:160-213):
 //                         numpy.dot + per-row numpy.argsort become one exact-fp32 MFMA GEMM whose
@@ -9,8 +9,8 @@
 //   cmhse_sim_rank_labelled  the same ranking against any set of positives per query, any gallery
 //                         size: a threshold pass over the (query, positive) pairs in the place of the
 //                         diagonal pass, then the same counting pass without the excluded column.
-//   cmhse_cosine_sim      loss.cosine_sim       (/root/reference/loss.py:12-13)
-//   cmhse_contrastive_fwd loss.ContrastiveLoss.forward (/root/reference/loss.py:86-117)
+//   cmhse_cosine_sim      loss.cosine_sim       (/root/reference/loss.py:12-13): the stored-score GEMM,
+//                         which the training losses of loss.hip launch through sim_store.hpp
 //
 // Bit-exactness of the ranks: every d[i][j] is produced by the same MFMA k-chain (nt_core.hpp:
 // the k order per output element does not depend on the tile position), so the diagonal values
@@ -25,7 +25,7 @@
 #include "gru_ws.hpp"
 #include "nt_core.hpp"
 #include "score_tile.hpp"
-#include "step_loss.hpp"
+#include "sim_store.hpp"
 
 namespace cmhse {
 
@@ -316,113 +316,9 @@ __global__ void label_decode_kernel(const score_key_t* key, float* thr, int32_t*
   if (best_score) best_score[i] = key_score(k);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Contrastive loss reduction over a stored n x n score matrix (loss.py:89-117).
-// Workgroup b < nrb reduces rows [64b, 64b+64) (cost_s); workgroup nrb + c reduces columns
-// [64c, 64c+64) (cost_im).  fp64 partial sums, fixed order -> bitwise reproducible.
-// ---------------------------------------------------------------------------------------------
-struct LossParams {
-  const float* scores;  // [n, n]
-  int32_t n, nrb;
-  float margin;
-  int32_t max_violation, norm;
-  double* partial;  // [2 * nrb]
-  float* loss;
-  const int32_t* blk_off;  // batched blocks (blockIdx.y): see SimParams
-  int64_t blk_stride;
-};
-
-__device__ __forceinline__ LossParams loss_block(const LossParams& q) {
-  LossParams p = q;
-  if (p.blk_off != nullptr) {
-    p.n = p.blk_off[blockIdx.y + 1] - p.blk_off[blockIdx.y];
-    p.scores += static_cast<int64_t>(blockIdx.y) * p.blk_stride;
-    p.partial += static_cast<int64_t>(blockIdx.y) * 2 * p.nrb;
-    p.loss += blockIdx.y;
-  }
-  return p;
-}
-
-__global__ __launch_bounds__(kThreads) void contrastive_partial_kernel(const LossParams p_) {
-  const LossParams p = loss_block(p_);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = p.n;
-  const float* S = p.scores;
-  __shared__ double s_part[kThreads];
-  double total = 0.0;
-  if (static_cast<int>(blockIdx.x) < p.nrb) {
-    // rows: one wave per row, lanes stride the columns
-    const int r0 = blockIdx.x * 64;
-    for (int i = r0 + wave; i < r0 + 64 && i < n; i += kThreads / 64) {
-      const float dii = S[static_cast<int64_t>(i) * n + i];
-      double sum = 0.0;
-      float mx = 0.f;
-      for (int j = lane; j < n; j += 64) {
-        float c = fmaxf(p.margin + S[static_cast<int64_t>(i) * n + j] - dii, 0.f);
-        if (j == i) c = 0.f;
-        sum += c;
-        mx = fmaxf(mx, c);
-      }
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) {
-        sum += __shfl_xor(sum, d, 64);
-        mx = fmaxf(mx, __shfl_xor(mx, d, 64));
-      }
-      total += p.max_violation ? static_cast<double>(mx) : sum;
-    }
-    s_part[tid] = (lane == 0) ? total : 0.0;
-  } else {
-    // columns: thread c < 64 owns column j (coalesced across the wave), 4 waves split the rows
-    const int j = (blockIdx.x - p.nrb) * 64 + lane;
-    double sum = 0.0;
-    float mx = 0.f;
-    if (j < n) {
-      const float djj = S[static_cast<int64_t>(j) * n + j];
-      for (int i = wave; i < n; i += kThreads / 64) {
-        float c = fmaxf(p.margin + S[static_cast<int64_t>(i) * n + j] - djj, 0.f);
-        if (i == j) c = 0.f;
-        sum += c;
-        mx = fmaxf(mx, c);
-      }
-    }
-    // combine the 4 waves' shares of each column, then the 64 columns
-    __shared__ double c_sum[kThreads];
-    __shared__ float c_max[kThreads];
-    c_sum[tid] = sum;
-    c_max[tid] = mx;
-    __syncthreads();
-    double v = 0.0;
-    if (wave == 0) {
-      const double cs = c_sum[lane] + c_sum[64 + lane] + c_sum[128 + lane] + c_sum[192 + lane];
-      const float cm = fmaxf(fmaxf(c_max[lane], c_max[64 + lane]),
-                             fmaxf(c_max[128 + lane], c_max[192 + lane]));
-      v = p.max_violation ? static_cast<double>(cm) : cs;
-    }
-    s_part[tid] = v;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int i = 0; i < kThreads; ++i) t += s_part[i];
-    p.partial[blockIdx.x] = t;
-  }
-}
-
-__global__ void contrastive_final_kernel(const LossParams p_) {
-  const LossParams p = loss_block(p_);
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    double cs = 0.0, ci = 0.0;
-    for (int b = 0; b < p.nrb; ++b) cs += p.partial[b];
-    for (int b = 0; b < p.nrb; ++b) ci += p.partial[p.nrb + b];
-    // loss.py:113-117: cost_s.sum() + cost_im.sum(), each an fp32 tensor sum
-    float loss = static_cast<float>(cs) + static_cast<float>(ci);
-    if (p.norm) loss = loss / static_cast<float>(static_cast<int64_t>(p.n) * p.n);
-    *p.loss = loss;
-  }
-}
-
-static int launch_sim_store(const float* A, const float* B, int n, int m, int D, float* scores,
-                            hipStream_t stream) {
+// The stored-score GEMM (sim_store.hpp): the one place that chooses its tile size.
+int launch_sim_store(const float* A, const float* B, int n, int m, int D, float* scores,
+                     hipStream_t stream, const int32_t* blk_off, int n_blocks, int64_t blk_stride) {
   SimParams p;
   p.A = A;
   p.B = B;
@@ -439,12 +335,12 @@ static int launch_sim_store(const float* A, const float* B, int n, int m, int D,
   p.rank = nullptr;
   p.top1key = nullptr;
   p.scores = scores;
-  p.blk_off = nullptr;
-  p.blk_stride = 0;
+  p.blk_off = blk_off;
+  p.blk_stride = blk_stride;
   const int64_t blocks = static_cast<int64_t>(p.n_tiles) * ((n + bt - 1) / bt);
   if (blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
   const size_t smem = small ? TileSmem<64, 64>::kBytes : TileSmem<kSimBM, kSimBN>::kBytes;
-  const dim3 grid(static_cast<unsigned>(blocks));
+  const dim3 grid(static_cast<unsigned>(blocks), n_blocks);
   if (small)
     return launch_tiles(sim_kernel<kSimStore, true, 1>, sim_kernel<kSimStore, false, 1>, D, grid, smem, stream, p);
   return launch_tiles(sim_kernel<kSimStore, true>, sim_kernel<kSimStore, false>, D, grid, smem, stream, p);
@@ -599,305 +495,6 @@ extern "C" int cmhse_cosine_sim(const float* im, const float* s, int32_t n, int3
   if (!im || !s || !scores || n <= 0 || m <= 0 || D <= 0) return CMHSE_ERR_ARG;
   const int rc = launch_sim_store(im, s, n, m, D, scores, static_cast<hipStream_t>(stream_));
   if (rc != CMHSE_OK) return rc;
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-extern "C" size_t cmhse_contrastive_workspace(int32_t n) {
-  if (n <= 0) return 0;
-  const size_t nrb = (n + 63) / 64;
-  return align256(static_cast<size_t>(n) * n * sizeof(float)) +
-         align256(2 * nrb * sizeof(double));
-}
-
-extern "C" int cmhse_contrastive_fwd(const float* im, const float* s, int32_t n, int32_t D,
-                                     float margin, int32_t max_violation, int32_t norm,
-                                     float* loss, float* scores_out, void* workspace,
-                                     size_t workspace_bytes, void* stream_) {
-  if (!im || !s || !loss || !workspace || n <= 0 || D <= 0) return CMHSE_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
-      workspace_bytes < cmhse_contrastive_workspace(n))
-    return CMHSE_ERR_WORKSPACE;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* scores = scores_out ? scores_out : static_cast<float*>(workspace);
-  const int rc = launch_sim_store(im, s, n, n, D, scores, stream);
-  if (rc != CMHSE_OK) return rc;
-  LossParams lp;
-  lp.scores = scores;
-  lp.n = n;
-  lp.nrb = (n + 63) / 64;
-  lp.margin = margin;
-  lp.max_violation = max_violation;
-  lp.norm = norm;
-  lp.partial = reinterpret_cast<double*>(static_cast<char*>(workspace) +
-                                         align256(static_cast<size_t>(n) * n * sizeof(float)));
-  lp.loss = loss;
-  lp.blk_off = nullptr;
-  lp.blk_stride = 0;
-  hipLaunchKernelGGL(contrastive_partial_kernel, dim3(2 * lp.nrb), dim3(kThreads), 0, stream, lp);
-  hipLaunchKernelGGL(contrastive_final_kernel, dim3(1), dim3(64), 0, stream, lp);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-extern "C" size_t cmhse_contrastive_blocks_workspace(int32_t n_blocks, int32_t max_n) {
-  if (n_blocks <= 0 || max_n <= 0) return 0;
-  const size_t nrb = (max_n + 63) / 64;
-  return align256(static_cast<size_t>(n_blocks) * max_n * max_n * sizeof(float)) +
-         align256(static_cast<size_t>(n_blocks) * 2 * nrb * sizeof(double));
-}
-
-extern "C" int cmhse_contrastive_blocks_fwd(const float* im, const float* s,
-                                            const int32_t* blk_off, int32_t n_blocks,
-                                            int32_t max_n, int32_t D, float margin,
-                                            int32_t max_violation, int32_t norm, float* losses,
-                                            void* workspace, size_t workspace_bytes,
-                                            void* stream_) {
-  if (!im || !s || !blk_off || !losses || !workspace || n_blocks <= 0 || max_n <= 0 || D <= 0)
-    return CMHSE_ERR_ARG;
-  if (n_blocks > 65535) return CMHSE_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
-      workspace_bytes < cmhse_contrastive_blocks_workspace(n_blocks, max_n))
-    return CMHSE_ERR_WORKSPACE;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SimParams p;
-  p.A = im;
-  p.B = s;
-  p.N = p.M = p.nrows = max_n;
-  p.D = D;
-  p.row0 = 0;
-  const bool small = max_n <= kSimSmallMax;
-  const int bt = small ? 64 : kSimBN;
-  p.n_tiles = (max_n + bt - 1) / bt;
-  p.group = 0;
-  p.diag = nullptr;
-  p.rank = nullptr;
-  p.top1key = nullptr;
-  p.scores = static_cast<float*>(workspace);
-  p.blk_off = blk_off;
-  p.blk_stride = static_cast<int64_t>(max_n) * max_n;
-  const unsigned tiles = static_cast<unsigned>(p.n_tiles) * ((max_n + bt - 1) / bt);
-  const size_t smem = small ? TileSmem<64, 64>::kBytes : TileSmem<kSimBM, kSimBN>::kBytes;
-  const dim3 grid(tiles, n_blocks);
-  const int rc =
-      small ? launch_tiles(sim_kernel<kSimStore, true, 1>, sim_kernel<kSimStore, false, 1>, D, grid, smem, stream, p)
-            : launch_tiles(sim_kernel<kSimStore, true>, sim_kernel<kSimStore, false>, D, grid, smem, stream, p);
-  if (rc != CMHSE_OK) return rc;
-  LossParams lp;
-  lp.scores = p.scores;
-  lp.n = max_n;
-  lp.nrb = (max_n + 63) / 64;
-  lp.margin = margin;
-  lp.max_violation = max_violation;
-  lp.norm = norm;
-  lp.partial = reinterpret_cast<double*>(
-      static_cast<char*>(workspace) +
-      align256(static_cast<size_t>(n_blocks) * max_n * max_n * sizeof(float)));
-  lp.loss = losses;
-  lp.blk_off = blk_off;
-  lp.blk_stride = p.blk_stride;
-  hipLaunchKernelGGL(contrastive_partial_kernel, dim3(2 * lp.nrb, n_blocks), dim3(kThreads), 0,
-                     stream, lp);
-  hipLaunchKernelGGL(contrastive_final_kernel, dim3(1, n_blocks), dim3(64), 0, stream, lp);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-// ---------------------------------------------------------------------------------------------
-// cmhse_step_losses_fwd: F.normalize of the step's encoder outputs written straight into the
-// row-blocked operands of the batched ContrastiveLoss, the losses, and their weighted total.
-// ---------------------------------------------------------------------------------------------
-struct StepNormParams {
-  const float* src[2][CMHSE_STEP_LOSS_MAX];  // [side][term]: the embedding that is the term's a / b
-  int32_t n[CMHSE_STEP_LOSS_MAX];            // term sizes
-  float weight[CMHSE_STEP_LOSS_MAX];
-  int32_t n_terms, D, R;
-  float* y[2];        // [R, D] each
-  int32_t* blk_off;   // [n_terms + 1]
-};
-
-// one workgroup per operand row (2R of them); the arithmetic of l2norm_rows_kernel, order included
-__global__ __launch_bounds__(kThreads) void step_norm_kernel(const StepNormParams p) {
-  const int side = (static_cast<int>(blockIdx.x) >= p.R) ? 1 : 0;
-  const int r = static_cast<int>(blockIdx.x) - side * p.R;
-  const float* xr = nullptr;
-  int off = 0;
-#pragma unroll
-  for (int k = 0; k < CMHSE_STEP_LOSS_MAX; ++k) {
-    if (k < p.n_terms) {
-      if (r >= off && r < off + p.n[k])
-        xr = (side ? p.src[1][k] : p.src[0][k]) + static_cast<int64_t>(r - off) * p.D;
-      off += p.n[k];
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    int o = 0;
-    p.blk_off[0] = 0;
-#pragma unroll
-    for (int k = 0; k < CMHSE_STEP_LOSS_MAX; ++k)
-      if (k < p.n_terms) {
-        o += p.n[k];
-        p.blk_off[k + 1] = o;
-      }
-  }
-  float* yr = p.y[side] + static_cast<int64_t>(r) * p.D;
-  float ss = 0.f;
-  for (int c = threadIdx.x; c < p.D; c += kThreads) {
-    const float v = xr[c];
-    ss += v * v;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
-  __shared__ float s_part[kThreads / 64];
-  __shared__ float s_inv;
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = ss;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int i = 0; i < kThreads / 64; ++i) t += s_part[i];
-    s_inv = 1.0f / fmaxf(sqrtf(t), 1e-12f);
-  }
-  __syncthreads();
-  const float inv = s_inv;
-  for (int c = threadIdx.x; c < p.D; c += kThreads) yr[c] = xr[c] * inv;
-}
-
-__global__ void step_total_kernel(const StepNormParams p, const float* values, float* total) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < CMHSE_STEP_LOSS_MAX; ++k)
-      if (k < p.n_terms) t += p.weight[k] * values[k];
-    *total = t;
-  }
-}
-
-// GroupWiseContrastiveLoss (loss.py:26-38): block (video i's clips x video j's captions) max or
-// mean of the clip x caption score matrix.  One workgroup per block; the arg-max (row-major first
-// maximum) is kept for the backward pass.
-struct BlockReduceParams {
-  const float* scores;  // [n, n]
-  const int32_t* row_off;
-  const int32_t* col_off;
-  float* reduced;   // [B, B]
-  int32_t* arg;     // [B, B] flat index r*n + c of the block maximum
-  int32_t n, B, use_max;
-};
-
-__global__ __launch_bounds__(kThreads) void block_reduce_kernel(const BlockReduceParams q) {
-  const int bi = blockIdx.y, bj = blockIdx.x, tid = threadIdx.x;
-  const int r0 = q.row_off[bi], r1 = q.row_off[bi + 1], c0 = q.col_off[bj], c1 = q.col_off[bj + 1];
-  const int w = c1 - c0, cnt = (r1 - r0) * w;
-  double sum = 0.0;
-  float best = -INFINITY;
-  int arg = 0x7fffffff;
-  for (int e = tid; e < cnt; e += kThreads) {
-    const int r = r0 + e / w, c = c0 + e % w;
-    const float v = q.scores[static_cast<int64_t>(r) * q.n + c];
-    sum += v;
-    const int flat = r * q.n + c;
-    if (v > best || (v == best && flat < arg)) {
-      best = v;
-      arg = flat;
-    }
-  }
-  __shared__ double s_sum[kThreads];
-  __shared__ float s_best[kThreads];
-  __shared__ int s_arg[kThreads];
-  s_sum[tid] = sum;
-  s_best[tid] = best;
-  s_arg[tid] = arg;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    float b = -INFINITY;
-    int a = 0x7fffffff;
-    for (int i = 0; i < kThreads; ++i) {
-      t += s_sum[i];
-      if (s_best[i] > b || (s_best[i] == b && s_arg[i] < a)) {
-        b = s_best[i];
-        a = s_arg[i];
-      }
-    }
-    q.reduced[bi * q.B + bj] = q.use_max ? b : static_cast<float>(t / cnt);
-    q.arg[bi * q.B + bj] = a;
-  }
-}
-
-extern "C" size_t cmhse_step_losses_workspace(const cmhse_step_losses* d) {
-  StepLossLayout L;
-  return step_loss_layout(d, &L) ? L.bytes : 0;
-}
-
-extern "C" int cmhse_step_losses_fwd(const cmhse_step_losses* d, float* values, float* total,
-                                     void* workspace, size_t workspace_bytes, void* stream_) {
-  StepLossLayout L;
-  if (!values || !total || !workspace || !step_loss_layout(d, &L)) return CMHSE_ERR_ARG;
-  for (int e = 0; e < d->n_emb; ++e)
-    if (!d->x[e]) return CMHSE_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 || workspace_bytes < L.bytes)
-    return CMHSE_ERR_WORKSPACE;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  StepNormParams p = {};
-  for (int k = 0; k < d->n_terms; ++k) {
-    p.src[0][k] = d->x[d->term_a[k]];
-    p.src[1][k] = d->x[d->term_b[k]];
-    p.n[k] = d->rows[d->term_a[k]];
-    p.weight[k] = d->weight[k];
-  }
-  p.n_terms = d->n_terms;
-  p.D = d->D;
-  p.R = L.R;
-  p.y[0] = reinterpret_cast<float*>(ws + L.y_im);
-  p.y[1] = reinterpret_cast<float*>(ws + L.y_s);
-  p.blk_off = reinterpret_cast<int32_t*>(ws + L.blk_off);
-  hipLaunchKernelGGL(step_norm_kernel, dim3(2u * L.R), dim3(kThreads), 0, stream, p);
-  const int rc = cmhse_contrastive_blocks_fwd(
-      p.y[0], p.y[1], p.blk_off, d->n_terms, L.max_n, d->D, d->margin, d->max_violation, d->norm,
-      values, ws + L.fwd_ws, cmhse_contrastive_blocks_workspace(d->n_terms, L.max_n), stream_);
-  if (rc != CMHSE_OK) return rc;
-  hipLaunchKernelGGL(step_total_kernel, dim3(1), dim3(64), 0, stream, p, values, total);
-  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
-}
-
-extern "C" size_t cmhse_groupwise_workspace(int32_t n, int32_t B) {
-  if (n <= 0 || B <= 0) return 0;
-  const size_t nrb = (B + 63) / 64;
-  return align256(static_cast<size_t>(n) * n * sizeof(float)) +
-         align256(2 * nrb * sizeof(double));
-}
-
-extern "C" int cmhse_groupwise_fwd(const float* im, const float* s, int32_t n, int32_t D,
-                                   const int32_t* row_off, const int32_t* col_off, int32_t B,
-                                   float margin, int32_t max_violation, int32_t norm, float* loss,
-                                   float* reduced, int32_t* arg, float* scores_out,
-                                   void* workspace, size_t workspace_bytes, void* stream_) {
-  if (!im || !s || !row_off || !col_off || !loss || !reduced || !arg || !workspace || n <= 0 ||
-      D <= 0 || B <= 0 || B > 65535)
-    return CMHSE_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
-      workspace_bytes < cmhse_groupwise_workspace(n, B))
-    return CMHSE_ERR_WORKSPACE;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* scores = scores_out ? scores_out : static_cast<float*>(workspace);
-  const int rc = launch_sim_store(im, s, n, n, D, scores, stream);
-  if (rc != CMHSE_OK) return rc;
-  BlockReduceParams bp;
-  bp.scores = scores; bp.row_off = row_off; bp.col_off = col_off; bp.reduced = reduced;
-  bp.arg = arg; bp.n = n; bp.B = B; bp.use_max = max_violation;
-  hipLaunchKernelGGL(block_reduce_kernel, dim3(B, B), dim3(kThreads), 0, stream, bp);
-  LossParams lp;
-  lp.scores = reduced;
-  lp.n = B;
-  lp.nrb = (B + 63) / 64;
-  lp.margin = margin;
-  lp.max_violation = max_violation;
-  lp.norm = norm;
-  lp.partial = reinterpret_cast<double*>(static_cast<char*>(workspace) +
-                                         align256(static_cast<size_t>(n) * n * sizeof(float)));
-  lp.loss = loss;
-  lp.blk_off = nullptr;
-  lp.blk_stride = 0;
-  hipLaunchKernelGGL(contrastive_partial_kernel, dim3(2 * lp.nrb), dim3(kThreads), 0, stream, lp);
-  hipLaunchKernelGGL(contrastive_final_kernel, dim3(1), dim3(64), 0, stream, lp);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }
 

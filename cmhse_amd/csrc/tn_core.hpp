@@ -5,6 +5,8 @@
 // ROW index of both operands.  Tiles are staged [k][m] in LDS exactly as they lie in memory
 // (coalesced float4 along m / n), and the MFMA fragments (A[i = lane&31][k = lane>>5]) are read
 // with ds_read_b32 — 32 consecutive lanes read 32 consecutive floats, conflict-free.
+// tn_mainloop is the tile loop (tn_rows.hpp builds the weight gradients on it); gemm_tn_kernel / launch_tn
+// are the plain product, single or batched over row blocks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -123,6 +125,81 @@ __device__ __forceinline__ void tn_mainloop(float* smem, const float* a_base, in
     if (c + 1 < nchunks) store(cur ^ 1);
     __syncthreads();
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// the plain TN product (the loss gradients, loss.hip)
+// ---------------------------------------------------------------------------------------------
+struct TnParams {
+  const float* a;  // [K, lda], columns m
+  int64_t lda;
+  const float* b;  // [K, ldb] or rows through b_addr
+  int64_t ldb;
+  const uint64_t* b_addr;
+  float* c;  // [M, ldc]
+  int64_t ldc;
+  int32_t M, N, n_tiles;
+  int64_t K;
+  const float* scale;  // optional device scalar multiplied into C
+  // several products in one launch (blockIdx.y = block b, rows blk_off[b] .. blk_off[b+1] of the
+  // caller's row-blocked operands): A is the block's [n_b, n_b] matrix at a + b * blk_stride
+  // (lda = n_b), B / C are rows blk_off[b].. of b / c; M = K = n_b
+  const int32_t* blk_off;
+  int64_t blk_stride;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void gemm_tn_kernel(const TnParams q_) {
+  TnParams q = q_;
+  if (q.blk_off != nullptr) {
+    const int b = blockIdx.y, off = q.blk_off[b], nb = q.blk_off[b + 1] - off;
+    q.a += b * q.blk_stride;
+    q.lda = nb;
+    q.b += static_cast<int64_t>(off) * q.ldb;
+    q.c += static_cast<int64_t>(off) * q.ldc;
+    q.M = nb;
+    q.K = nb;
+    if ((blockIdx.x / q.n_tiles) * 128 >= nb) return;   // M tile outside this (smaller) block
+  }
+  constexpr int BM = 128, BN = 128;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int n0 = (blockIdx.x % q.n_tiles) * BN, m0 = (blockIdx.x / q.n_tiles) * BM;
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = zero16();
+  tn_mainloop<BM, BN, VEC>(smem, q.a, q.lda, q.M, q.b, q.ldb, q.b_addr, q.N, q.K, m0, n0, acc);
+  const float sc = q.scale ? *q.scale : 1.0f;
+#pragma unroll
+  for (int ms = 0; ms < 2; ++ms)
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 64 + ms * 32 + acc_row(r, lane);
+        const int n = n0 + wn * 64 + ns * 32 + acc_col(lane);
+        if (m < q.M && n < q.N) q.c[static_cast<int64_t>(m) * q.ldc + n] = sc * acc[ms][ns][r];
+      }
+}
+
+// blk_off != nullptr: n_blocks products in one launch (blockIdx.y), M = K = max_n bounding every block
+static inline void launch_tn(const float* a, int64_t lda, const float* b, int64_t ldb,
+                             const uint64_t* b_addr, float* c, int64_t ldc, int M, int N, int64_t K,
+                             const float* scale, bool vec, hipStream_t st,
+                             const int32_t* blk_off = nullptr, int n_blocks = 1, int64_t blk_stride = 0) {
+  TnParams q;
+  q.a = a; q.lda = lda; q.b = b; q.ldb = ldb; q.b_addr = b_addr; q.c = c; q.ldc = ldc;
+  q.M = M; q.N = N; q.K = K; q.n_tiles = (N + 127) / 128; q.scale = scale;
+  q.blk_off = blk_off; q.blk_stride = blk_stride;
+  const dim3 grid(static_cast<unsigned>(q.n_tiles) * ((M + 127) / 128), n_blocks);
+  const size_t smem = TnSmem<128, 128>::kBytes;
+  if (vec)
+    hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(kThreads), smem, st, q);
+  else
+    hipLaunchKernelGGL(gemm_tn_kernel<false>, grid, dim3(kThreads), smem, st, q);
 }
 
 }  // namespace cmhse

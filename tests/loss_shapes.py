@@ -17,7 +17,7 @@ CSRC = os.path.join(REPO, 'cmhse_amd', 'csrc')
 # constants of the sources the tables rely on (checked by tests/test_loss_shapes_cpu.py)
 K_THREADS = 256        # nt_core.hpp kThreads: the stride of the group-wise block loops
 SIM_SMALL_MAX = 512    # sim.hip kSimSmallMax: stored-score matrices above it use 128 x 128 tiles
-LOSS_BLOCK_ROWS = 64   # sim.hip (n + 63) / 64: rows per workgroup of contrastive_partial_kernel
+LOSS_BLOCK_ROWS = 64   # loss_layout.hpp (n + 63) / 64: rows per workgroup of contrastive_partial_kernel
 STEP_LOSS_MAX = 8      # cmhse_hip.h CMHSE_STEP_LOSS_MAX
 
 DYADIC_MARGIN = 0.25
@@ -36,14 +36,15 @@ def source_constants():
     m = re.findall(pattern, text)
     assert len(m) == 1, (pattern, m)
     return m[0]
-  sim, bwd = read(CSRC, 'sim.hip'), read(CSRC, 'bwd.hip')
-  gw_fwd = sim[sim.index('extern "C" int cmhse_groupwise_fwd'):]
-  gw_bwd = bwd[bwd.index('extern "C" int cmhse_groupwise_bwd'):]
+  sim, loss, layout = read(CSRC, 'sim.hip'), read(CSRC, 'loss.hip'), read(CSRC, 'loss_layout.hpp')
+  gw_fwd = layout[layout.index('LossFwdLayout groupwise_fwd_layout('):]    # the group-wise loss's nrb
+  gw_fwd = gw_fwd[:gw_fwd.index('\n}\n')]
+  gw_bwd = loss[loss.index('extern "C" int cmhse_groupwise_bwd'):]
   gw_bwd = gw_bwd[:gw_bwd.index('\n}\n')]
   return dict(
       kThreads=int(const(read(CSRC, 'nt_core.hpp'), r'constexpr int kThreads = (\d+);')),
       kSimSmallMax=int(const(sim, r'constexpr int kSimSmallMax = (\d+);')),
-      loss_blocks=const(gw_fwd, r'lp\.nrb = (\(B \+ 63\) / 64);'),
+      loss_blocks=const(gw_fwd, r'loss_fwd_layout\([^;]*, (\(B \+ 63\) / 64)\);'),
       vec=const(gw_bwd, r'const bool vec = ([^;]+);'),
       step_loss_max=int(const(read(REPO, 'include', 'cmhse_hip.h'), r'#define CMHSE_STEP_LOSS_MAX (\d+)')))
 

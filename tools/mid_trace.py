@@ -23,10 +23,11 @@ def main():
   T = int(argv[1]) if len(argv) > 1 else 12
   I = int(argv[2]) if len(argv) > 2 else 500
   H = int(argv[3]) if len(argv) > 3 else 1024
+  from cmhse_amd.build import SOURCES      # every translation unit of the library
   csrc = os.path.join(ROOT, 'cmhse_amd', 'csrc')
   lib_path = os.path.join(ROOT, 'cmhse_amd', 'libcmhse_trace.so')
   cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
-         '-DTILE_TRACE_BUILD', '-o', lib_path] + [os.path.join(csrc, f) for f in ('gru.hip', 'sim.hip', 'bwd.hip')]
+         '-DTILE_TRACE_BUILD', '-o', lib_path] + [os.path.join(csrc, f) for f in SOURCES]
   srcs = [os.path.join(csrc, f) for f in os.listdir(csrc)]
   stale = not os.path.exists(lib_path) or \
       os.path.getmtime(lib_path) < max(os.path.getmtime(p) for p in srcs)

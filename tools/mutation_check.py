@@ -39,7 +39,7 @@ MUTANTS = {
     'attn_eps_fwd': ('gru_attention.hpp', 's_den = d + 0.0001f;', 's_den = d + 0.0f;'),
     'attn_eps_bwd': ('bwd_pool_kernels.hpp', 's_den = d + 0.0001f;', 's_den = d + 0.0f;'),
     # loss.py:114-115: `norm` divides by n * m, not by n
-    'norm_by_n': ('sim.hip', 'loss = loss / static_cast<float>(static_cast<int64_t>(p.n) * p.n);',
+    'norm_by_n': ('loss_kernels.hpp', 'loss = loss / static_cast<float>(static_cast<int64_t>(p.n) * p.n);',
                   'loss = loss / static_cast<float>(p.n);'),
     # nn.GRU: n = tanh(W_in x + b_in + r * (W_hn h + b_hn)) — b_hn INSIDE the reset gate's product
     # (the mid-size step kernel, the one the golden-sized batches run on)
@@ -52,11 +52,11 @@ MUTANTS = {
     'rank_counts_ties': ('sim.hip', 'valid && (MODE == kSimLabel || j != gi) && v > dii',
                          'valid && (MODE == kSimLabel || j != gi) && v >= dii'),
     # loss.py:100-103: the diagonal of both cost matrices is masked to zero
-    'loss_diag_not_masked': ('sim.hip', 'if (j == i) c = 0.f;', ''),
+    'loss_diag_not_masked': ('loss_kernels.hpp', 'if (j == i) c = 0.f;', ''),
     # loss.py:106-111: max_violation keeps the hardest negative per row / column only
-    'max_violation_sums': ('sim.hip', 'total += p.max_violation ? static_cast<double>(mx) : sum;', 'total += sum;'),
+    'max_violation_sums': ('loss_kernels.hpp', 'total += p.max_violation ? static_cast<double>(mx) : sum;', 'total += sum;'),
     # F.normalize's eps (model.py l2norm of the encoder outputs): a zero row stays zero, x / max(|x|, 1e-12)
-    'l2norm_eps': ('gru_rows.hpp', 's_inv = 1.0f / fmaxf(sqrtf(t), 1e-12f);', 's_inv = 1.0f / sqrtf(t);'),
+    'l2norm_eps': ('norm_rows.hpp', 's_inv = 1.0f / fmaxf(sqrtf(t), 1e-12f);', 's_inv = 1.0f / sqrtf(t);'),
     # BPTT step shapes (tests/test_gpu_bptt_shapes.py): value-only edits, no address, grid or barrier moves.
     # The 32 x 32 step tile's LDS combine adds the partials of 4 waves only: wrong for the 8-wave kernels
     'bwd_step_combine_4_waves': ('bwd_step_kernels.hpp', 'for (int w = 0; w < NW; ++w) part += red[w][reg][lb + j];',
@@ -87,17 +87,17 @@ MUTANTS = {
     'scalar_k_remainder': ('nt_core.hpp', 'v.w = (valid && k + 3 < klim) ? v.w : 0.f;', 'v.w = valid ? v.w : 0.f;'),
     # loss kernels at training shapes (tests/test_gpu_loss_shapes.py): value-only edits as above.
     # block_reduce_kernel visits a thread's first element only: wrong for blocks of more than 256 elements
-    'gw_reduce_first_trip': ('sim.hip', 'for (int e = tid; e < cnt; e += kThreads) {', 'if (int e = tid; e < cnt) {'),
+    'gw_reduce_first_trip': ('loss_kernels.hpp', 'for (int e = tid; e < cnt; e += kThreads) {', 'if (int e = tid; e < cnt) {'),
     # ... its per-thread scan keeps the LAST of a thread's tied maxima (loss.py:31 torch.max: the first)
-    'gw_argmax_last_tie': ('sim.hip', 'if (v > best || (v == best && flat < arg)) {',
+    'gw_argmax_last_tie': ('loss_kernels.hpp', 'if (v > best || (v == best && flat < arg)) {',
                            'if (v > best || (v == best && flat > arg)) {'),
     # the block mean's gradient divides by the block's width instead of its element count
-    'gw_expand_mean_by_width': ('bwd_loss_kernels.hpp', 'g / static_cast<float>(cnt);', 'g / static_cast<float>(w);'),
+    'gw_expand_mean_by_width': ('loss_kernels.hpp', 'g / static_cast<float>(cnt);', 'g / static_cast<float>(w);'),
     # groupwise_expand_kernel writes a thread's first element only
-    'gw_expand_first_trip': ('bwd_loss_kernels.hpp', 'for (int e = threadIdx.x; e < cnt; e += kThreads) {',
+    'gw_expand_first_trip': ('loss_kernels.hpp', 'for (int e = threadIdx.x; e < cnt; e += kThreads) {',
                              'if (int e = threadIdx.x; e < cnt) {'),
     # decoder/loss.py:24: the mean is over the rows
-    'euclid_norm_by_cols': ('bwd_loss_kernels.hpp', 'if (q.norm) sc /= static_cast<float>(q.rows);',
+    'euclid_norm_by_cols': ('loss_kernels.hpp', 'if (q.norm) sc /= static_cast<float>(q.rows);',
                             'if (q.norm) sc /= static_cast<float>(q.cols);'),
 }
 # the tests that must kill them (and pass on the product library)

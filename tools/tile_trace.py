@@ -86,11 +86,12 @@ def main():
   S = int(argv[0]) if len(argv) > 0 else 22419
   I = int(argv[1]) if len(argv) > 1 else 500
   H = int(argv[2]) if len(argv) > 2 else 1024
+  from cmhse_amd.build import SOURCES      # every translation unit of the library
   csrc = os.path.join(ROOT, 'cmhse_amd', 'csrc')
   lib_path = os.path.join(ROOT, 'cmhse_amd', os.environ.get('TRACE_LIB', 'libcmhse_trace.so'))
   cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
-         '-DTILE_TRACE_BUILD'] + os.environ.get('TRACE_FLAGS', '').split() + ['-o', lib_path] + [os.path.join(csrc, f) for f in
-                                              ('gru.hip', 'sim.hip', 'bwd.hip')]
+         '-DTILE_TRACE_BUILD'] + os.environ.get('TRACE_FLAGS', '').split() + ['-o', lib_path] + \
+      [os.path.join(csrc, f) for f in SOURCES]
   srcs = [os.path.join(csrc, f) for f in os.listdir(csrc)]
   stale = not os.path.exists(lib_path) or \
       os.path.getmtime(lib_path) < max(os.path.getmtime(p) for p in srcs)
