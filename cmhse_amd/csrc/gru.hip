@@ -239,6 +239,12 @@ extern "C" int cmhse_gru_pool_ws_region(int32_t S, int32_t Tmax, int64_t sum_T, 
     *offset = L.argmax, *bytes = L.v > L.argmax ? static_cast<size_t>(S) * H * sizeof(int32_t) : 0;
   } else if (!strcmp(name, "v")) {
     *offset = L.v, *bytes = L.wih_s > L.v ? static_cast<size_t>(sum_T) * H * sizeof(float) : 0;
+  } else if (!strcmp(name, "xs")) {      // bf16x3: the pre-split rows (dwords; 0 bytes in the exact mode)
+    *offset = L.xs, *bytes = L.hs_s > L.xs ? static_cast<size_t>(sum_T) * split_ld(I) * sizeof(float) : 0;
+  } else if (!strcmp(name, "hs_s")) {
+    *offset = L.hs_s, *bytes = L.h0_s > L.hs_s ? static_cast<size_t>(sum_T) * split_ld(H) * sizeof(float) : 0;
+  } else if (!strcmp(name, "h0_s")) {
+    *offset = L.h0_s, *bytes = L.gx > L.h0_s ? static_cast<size_t>(S) * split_ld(H) * sizeof(float) : 0;
   } else {
     return CMHSE_ERR_ARG;
   }

@@ -742,8 +742,10 @@ def gru_pool_fwd_multi(requests, tail_stream=None, job_streams=None, join=True, 
 def saved_region(fctx, name):
   """A named region of a forward call's workspace (cmhse_gru_pool_ws_region) as a tensor view:
   'hs' [sum_T, H], 'gates' [sum_T, 4H], 'v' [sum_T, H] float32, 'argmax' [S, H] int32 (rows in the
-  schedule's SORTED order: fctx['sched'].order maps them to input order).  None when the call's mode
-  did not keep it.  For tests and tools."""
+  schedule's SORTED order: fctx['sched'].order maps them to input order); in the bf16x3 math mode also
+  the pre-split rows as int32 dwords (8 of bf16 hi pairs, then 8 of lo pairs per 16 k): 'xs' [sum_T,
+  split_ld(I)], 'hs_s' [sum_T, split_ld(H)] (rows of the bf16x3 steps only) and 'h0_s' [S, split_ld(H)].
+  None when the call's mode did not keep it.  For tests and tools."""
   lib = _lib.load()
   sched, H, I = fctx['sched'], fctx['H'], fctx['I']
   flags = fctx.get('mode_flags', fctx['pool_mode'])
@@ -756,6 +758,8 @@ def saved_region(fctx, name):
   raw = fctx['ws'][off.value:off.value + nbytes.value]
   if name == 'argmax':
     return raw.view(torch.int32).view(sched.S, H)
+  if name in ('xs', 'hs_s', 'h0_s'):
+    return raw.view(torch.int32).view(sched.S if name == 'h0_s' else sched.sum_T, -1)
   return raw.view(torch.float32).view(-1, 4 * H if name == 'gates' else H)
 
 

@@ -176,8 +176,11 @@ size_t cmhse_gru_pool_workspace_tok(int32_t S, int32_t Tmax, int64_t sum_T, int3
  * forward kept: the gate activations, the arg-max step of the max pooling ...).  name: "hs"
  * [sum_T, H] f32 | "gates" [sum_T, 4H] f32 (r, z, n, W_hn h + b_hn) | "argmax" [S, H] int32, rows in
  * SORTED sequence order (CMHSE_POOL_MAX with CMHSE_SAVE_FOR_BACKWARD) | "v" [sum_T, H] f32
- * (CMHSE_POOL_ATTN with CMHSE_SAVE_FOR_BACKWARD).  *bytes = 0 when the mode does not keep the
- * region.  Unknown name: CMHSE_ERR_ARG.  No effect on any computation. */
+ * (CMHSE_POOL_ATTN with CMHSE_SAVE_FOR_BACKWARD) | with CMHSE_MATH_BF16X3 the pre-split rows, dwords
+ * of bf16 pairs, rows of K rounded up to whole 16-k chunks (per chunk 8 dwords of hi pairs, then 8 of
+ * lo pairs): "xs" [sum_T, ..] the inputs, "hs_s" [sum_T, ..] the hidden states (only the rows of the
+ * bf16x3 steps are written), "h0_s" [S, ..] the initial states.  *bytes = 0 when the mode does not
+ * keep the region.  Unknown name: CMHSE_ERR_ARG.  No effect on any computation. */
 int cmhse_gru_pool_ws_region(int32_t S, int32_t Tmax, int64_t sum_T, int32_t I, int32_t H,
                              int32_t pool_mode, const char* name, size_t* offset, size_t* bytes);
 

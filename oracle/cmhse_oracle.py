@@ -42,9 +42,69 @@ def _sigmoid(x):
 # :169-172,192-194 (Maxout).  pack_padded_sequence (layers.py:52,97,190) only reorders the
 # sequences; each sequence is independent, so the oracle masks by `t < len` instead of sorting.
 # --------------------------------------------------------------------------------------------
-def gru_forward(x, lens, w_ih, w_hh, b_ih, b_hh, h0=None, dtype=np.float32):
+# --------------------------------------------------------------------------------------------
+# The product library's opt-in bf16x3 math mode (no counterpart in the reference): a matrix product
+# of fp32 operands as three bf16 products, a b ~= a_hi b_hi + a_hi b_lo + a_lo b_hi with
+# x_hi = bf16(x), x_lo = bf16(x - x_hi), both rounded to nearest even.  Emulated here in float64, so
+# that a kernel of that mode has a yardstick that differs from it in fp32 accumulation order only.
+# --------------------------------------------------------------------------------------------
+def _bf16_bits(x, rounding='nearest'):
+  """The bf16 image (uint32, in the low 16 bits) of fp32 values: round to nearest even, or truncate
+  (`rounding='truncate'`, for tests that need a wrong split).  Finite inputs."""
+  u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+  if rounding == 'truncate':
+    return u >> np.uint32(16)
+  return (u + np.uint32(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)
+
+
+def split_bf16x3(x, rounding='nearest'):
+  """(hi, lo) of fp32 values, as float32 arrays: hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in
+  fp32), in NumPy integer arithmetic."""
+  x = np.ascontiguousarray(x, dtype=np.float32)
+  hi = (_bf16_bits(x, rounding) << np.uint32(16)).view(np.float32)
+  lo = (_bf16_bits(x - hi, rounding) << np.uint32(16)).view(np.float32)
+  return hi, lo
+
+
+def split_rows_bits(x, K):
+  """The uint32 image [rows, ceil(K / 16) * 16] of pre-split rows x [rows, K] as the library's
+  producers write them: per chunk of 16 k, 8 dwords of hi pairs (k even in the low half) then 8 dwords
+  of lo pairs; k >= K reads zero."""
+  x = np.ascontiguousarray(x, dtype=np.float32)
+  R, ld = x.shape[0], (K + 15) // 16 * 16
+  pad = np.zeros((R, ld), dtype=np.float32)
+  pad[:, :K] = x[:, :K]
+  hi, lo = split_bf16x3(pad)
+  out = np.empty((R, ld // 16, 16), dtype=np.uint32)
+  for half, part in ((0, hi), (8, lo)):
+    b = (part.view(np.uint32) >> np.uint32(16)).reshape(R, ld // 16, 8, 2)
+    out[:, :, half:half + 8] = b[..., 0] | (b[..., 1] << np.uint32(16))
+  return out.reshape(R, ld)
+
+
+def matmul_nt(a, b, products=None):
+  """a b^T in the arrays' own type; `products`: 'bf16x3' — the three-term split product of the
+  operands' fp32 values, summed in float64 ('bf16x3-truncate', 'bf16x3-two-terms': the same with a
+  truncating split / without a_lo b_hi, the wrong kernels a test must tell from the right one)."""
+  if products is None:
+    return a @ b.T
+  assert products in ('bf16x3', 'bf16x3-truncate', 'bf16x3-two-terms'), products
+  rounding = 'truncate' if products == 'bf16x3-truncate' else 'nearest'
+  (ah, al), (bh, bl) = split_bf16x3(a, rounding), split_bf16x3(b, rounding)
+  ah, al, bh, bl = (v.astype(np.float64) for v in (ah, al, bh, bl))
+  out = ah @ bh.T + ah @ bl.T
+  return out if products == 'bf16x3-two-terms' else out + al @ bh.T
+
+
+def gru_forward(x, lens, w_ih, w_hh, b_ih, b_hh, h0=None, dtype=np.float32, products=None, split_steps=0):
   """x [S,T,I] zero-padded, lens [S] ints (>=1).  Returns hs [S,T,H] (zeros at t >= len, like
-  pad_packed_sequence, layers.py:103) and h_last [S,H] (= h at t = len-1)."""
+  pad_packed_sequence, layers.py:103) and h_last [S,H] (= h at t = len-1).
+  `products` (see matmul_nt; needs dtype float64): both matrix products of the first `split_steps`
+  time steps are the emulated bf16x3 ones — the caller says which steps the library serves with its
+  bf16x3 kernel — and the hidden state is rounded to fp32 after EVERY step, as the library keeps it."""
+  if products is not None:
+    assert dtype == np.float64
+    return _gru_forward_split(x, lens, w_ih, w_hh, b_ih, b_hh, h0, products, split_steps)
   x = np.asarray(x, dtype=dtype)
   lens = np.asarray(lens).astype(np.int64)
   w_ih = np.asarray(w_ih, dtype=dtype); w_hh = np.asarray(w_hh, dtype=dtype)
@@ -69,6 +129,33 @@ def gru_forward(x, lens, w_ih, w_hh, b_ih, b_hh, h0=None, dtype=np.float32):
   return hs, h
 
 
+def _gru_forward_split(x, lens, w_ih, w_hh, b_ih, b_hh, h0, products, split_steps):
+  x = np.asarray(x, dtype=np.float32)
+  lens = np.asarray(lens).astype(np.int64)
+  w_ih, w_hh = np.asarray(w_ih, dtype=np.float32), np.asarray(w_hh, dtype=np.float32)
+  b_ih, b_hh = np.asarray(b_ih, dtype=np.float64), np.asarray(b_hh, dtype=np.float64)
+  S, T, I = x.shape
+  H = w_hh.shape[1]
+  h = np.zeros((S, H), dtype=np.float32) if h0 is None else np.array(h0, dtype=np.float32)
+  hs = np.zeros((S, T, H), dtype=np.float64)
+  w64 = w_ih.astype(np.float64), w_hh.astype(np.float64)
+  for t in range(int(lens.max())):
+    act = np.nonzero(lens > t)[0]
+    if t < split_steps:
+      g = matmul_nt(x[act, t], w_ih, products) + b_ih
+      gh = matmul_nt(h[act], w_hh, products) + b_hh
+    else:
+      g = x[act, t].astype(np.float64) @ w64[0].T + b_ih
+      gh = h[act].astype(np.float64) @ w64[1].T + b_hh
+    r = _sigmoid(g[:, :H] + gh[:, :H])
+    z = _sigmoid(g[:, H:2 * H] + gh[:, H:2 * H])
+    n = np.tanh(g[:, 2 * H:] + r * gh[:, 2 * H:])
+    hn = ((1.0 - z) * n + z * h[act]).astype(np.float32)
+    h[act] = hn
+    hs[act, t] = hn
+  return hs, h.astype(np.float64)
+
+
 def seq2seq_forward(x, lens, p, h0=None, dtype=np.float32):
   """layers.Seq2Seq.forward, /root/reference/layers.py:47-66: final hidden state."""
   _, h_last = gru_forward(x, lens, p['rnn.rnn.weight_ih_l0'], p['rnn.rnn.weight_hh_l0'],
@@ -87,13 +174,14 @@ def maxout_forward(x, lens, p, h0=None, dtype=np.float32):
   return np.where(mask, hs, -np.inf).max(axis=1).astype(dtype)
 
 
-def attention_energies(hs, p, dtype=np.float32):
-  """e = att_w(tanh(lin(h))), /root/reference/layers.py:105-106."""
+def attention_energies(hs, p, dtype=np.float32, products=None):
+  """e = att_w(tanh(lin(h))), /root/reference/layers.py:105-106.  `products` (see matmul_nt): the
+  projection lin(h) is the emulated bf16x3 product of the fp32 values of hs and of the weight."""
   S, T, H = hs.shape
   w_lin = np.asarray(p['rnn.lin.weight'], dtype=dtype)
   b_lin = np.asarray(p['rnn.lin.bias'], dtype=dtype)
   w_att = np.asarray(p['rnn.att_w.weight'], dtype=dtype).reshape(-1)
-  emb_h = np.tanh(hs.reshape(S * T, H) @ w_lin.T + b_lin)
+  emb_h = np.tanh(matmul_nt(hs.reshape(S * T, H), w_lin, products) + b_lin)
   return (emb_h @ w_att).reshape(S, T).astype(dtype)
 
 
@@ -112,9 +200,28 @@ def attention_forward(x, lens, p, h0=None, dtype=np.float32):
   return (att[:, :, None] * hs).sum(axis=1).astype(dtype)
 
 
-def pooled_gru_forward(rnn_type, x, lens, p, h0=None, dtype=np.float32):
+def pooled_gru_forward(rnn_type, x, lens, p, h0=None, dtype=np.float32, products=None, split_steps=0,
+                       split_attention=False):
   """Dispatch on `rnn_type` as model.EncoderImage/EncoderSequence do,
-  /root/reference/model.py:27-34,50-57."""
+  /root/reference/model.py:27-34,50-57.  `products` (see matmul_nt; float64 only) emulates the
+  library's bf16x3 mode: the first `split_steps` time steps and, with `split_attention`, the
+  attention projection use the split products.  Returns (out, hs [S, Tmax, H]) then."""
+  if products is not None:
+    assert dtype == np.float64
+    hs, h_last = gru_forward(x, lens, p['rnn.rnn.weight_ih_l0'], p['rnn.rnn.weight_hh_l0'],
+                             p['rnn.rnn.bias_ih_l0'], p['rnn.rnn.bias_hh_l0'], h0, dtype, products, split_steps)
+    lens = np.asarray(lens).astype(np.int64)
+    hs = hs[:, :int(lens.max())]
+    mask = np.arange(hs.shape[1])[None, :] < lens[:, None]
+    if rnn_type == 'seq2seq':
+      return h_last, hs
+    if rnn_type == 'maxout':
+      return np.where(mask[:, :, None], hs, -np.inf).max(axis=1), hs
+    if rnn_type != 'attention':
+      raise ValueError('Unsupported RNN type')
+    ex = np.exp(attention_energies(hs, p, dtype, products if split_attention else None)) * mask
+    att = ex / (ex.sum(axis=1, keepdims=True) + 0.0001)
+    return (att[:, :, None] * hs).sum(axis=1), hs
   if rnn_type == 'attention':
     return attention_forward(x, lens, p, h0, dtype)
   if rnn_type == 'seq2seq':

@@ -76,10 +76,9 @@ def _id(case):
   return '%s[%s]' % (case[0], ','.join(sorted(t.replace(' ', '_') for t in case[5])))
 
 
-@pytest.mark.parametrize('case', fwd_shapes.CASES, ids=[_id(c) for c in fwd_shapes.CASES])
-def test_fwd_step_shape_vs_oracle(dev, oracle, tune, case):
-  from cmhse_amd import evaluation, layers, ops
-  name, knobs, train, tail_stream, jobs, _ = case
+def _setup(jobs, dev):
+  """The layers of a case's requests (on `dev`), their float64 state dicts, the inputs (_inputs) and
+  the case's random stream."""
   rng = np.random.RandomState(sum(j['counts'][0] + 3 * j['H'] for j in jobs))
   layers_, sds, data = [], [], []
   for k, j in enumerate(jobs):
@@ -87,38 +86,53 @@ def test_fwd_step_shape_vs_oracle(dev, oracle, tune, case):
     sds.append({'rnn.' + n: v.detach().numpy().astype(np.float64) for n, v in layer.state_dict().items()})
     layers_.append(layer.to(dev))
     data.append(_inputs(j, rng, dev))
+  return layers_, sds, data, rng
+
+
+def _run_inference(jobs, layers_, data, dev, tail_stream):
+  """One ops.gru_pool_fwd_multi call of a case, finished: [(out, forward context)] per request."""
+  from cmhse_amd import evaluation, ops
+  keep, reqs = [], []
+  for j, layer, (lens, x, h0, tok, table) in zip(jobs, layers_, data):
+    w_lin, b_lin, w_att = layer._extra_weights()
+    weights = dict(w_ih=layer.rnn.weight_ih_l0.detach(), w_hh=layer.rnn.weight_hh_l0.detach(),
+                   b_ih=layer.rnn.bias_ih_l0.detach(), b_hh=layer.rnn.bias_hh_l0.detach())
+    if j['pool'] == 'ATTN':
+      weights.update(w_lin=w_lin.detach(), b_lin=b_lin.detach(), w_att=w_att.detach().reshape(-1))
+    req = dict(weights=weights, pool_mode=getattr(ops, 'POOL_' + j['pool']), lens=lens, I=j['I'], H=j['H'],
+               device=dev)
+    if tok is not None:
+      tt, tb = torch.from_numpy(tok).to(dev), torch.from_numpy(table).to(dev)
+      keep += [tt, tb]
+      req.update(tok_ptrs=ops.padded_row_ptrs(tt), emb_table=tb)
+    else:
+      xt = torch.from_numpy(x).to(dev)
+      keep.append(xt)
+      req['x_ptrs'] = ops.padded_row_ptrs(xt)
+    if h0 is not None:
+      ht = torch.from_numpy(h0).to(dev)
+      keep.append(ht)
+      req['h0_ptrs'] = ops.padded_row_ptrs(ht)
+    if j['plan'] is not None:
+      req['step_plan'] = np.asarray(j['plan'], dtype=np.int32)
+    reqs.append(req)
+  res = ops.gru_pool_fwd_multi(reqs, tail_stream=evaluation._tail_stream(dev) if tail_stream else None)
+  torch.cuda.synchronize()
+  del keep
+  return res
+
+
+@pytest.mark.parametrize('case', fwd_shapes.CASES, ids=[_id(c) for c in fwd_shapes.CASES])
+def test_fwd_step_shape_vs_oracle(dev, oracle, tune, case):
+  from cmhse_amd import layers, ops
+  name, knobs, train, tail_stream, jobs, _ = case
+  layers_, sds, data, rng = _setup(jobs, dev)
   tune(**knobs)
   ws = [rng.standard_normal((int(d[0].sum()) if j['pool'] == 'ALL' else len(d[0]), j['H'])).astype(np.float32)
         for j, d in zip(jobs, data)]
 
   def run_inference():
-    keep, reqs = [], []
-    for j, layer, (lens, x, h0, tok, table) in zip(jobs, layers_, data):
-      w_lin, b_lin, w_att = layer._extra_weights()
-      weights = dict(w_ih=layer.rnn.weight_ih_l0.detach(), w_hh=layer.rnn.weight_hh_l0.detach(),
-                     b_ih=layer.rnn.bias_ih_l0.detach(), b_hh=layer.rnn.bias_hh_l0.detach())
-      if j['pool'] == 'ATTN':
-        weights.update(w_lin=w_lin.detach(), b_lin=b_lin.detach(), w_att=w_att.detach().reshape(-1))
-      req = dict(weights=weights, pool_mode=getattr(ops, 'POOL_' + j['pool']), lens=lens, I=j['I'], H=j['H'],
-                 device=dev)
-      if tok is not None:
-        tt, tb = torch.from_numpy(tok).to(dev), torch.from_numpy(table).to(dev)
-        keep += [tt, tb]
-        req.update(tok_ptrs=ops.padded_row_ptrs(tt), emb_table=tb)
-      else:
-        xt = torch.from_numpy(x).to(dev)
-        keep.append(xt)
-        req['x_ptrs'] = ops.padded_row_ptrs(xt)
-      if h0 is not None:
-        ht = torch.from_numpy(h0).to(dev)
-        keep.append(ht)
-        req['h0_ptrs'] = ops.padded_row_ptrs(ht)
-      if j['plan'] is not None:
-        req['step_plan'] = np.asarray(j['plan'], dtype=np.int32)
-      reqs.append(req)
-    res = ops.gru_pool_fwd_multi(reqs, tail_stream=evaluation._tail_stream(dev) if tail_stream else None)
-    torch.cuda.synchronize()
-    return [[o.clone()] for o, _ in res]
+    return [[o.clone()] for o, _ in _run_inference(jobs, layers_, data, dev, tail_stream)]
 
   def run_training():
     calls, ins = [], []

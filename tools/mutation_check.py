@@ -25,6 +25,11 @@ Mutants:
                  the loss kernels at training shapes (killed by tests/test_gpu_loss_shapes.py; of the four
                  group-wise ones only the mean by width is caught by an older test:
                  profiles/loss_shapes_mutation_check.txt)
+  bf3_ring_reload_last_but_one, bf3_epilogue_odd_lo, bf3_attn_ring_past_cut, bf3_split_rows_truncates,
+  bf3_h0_ignored, bf3_tiled_wgs_counts_bf3
+                 the bf16x3 math mode (killed by tests/test_gpu_bf3_shapes.py — the last one changes the
+                 exact neighbour's tile height only, which no result can show:
+                 profiles/bf3_shapes_mutation_check.txt)
 """
 import os
 import shutil
@@ -99,14 +104,37 @@ MUTANTS = {
     # decoder/loss.py:24: the mean is over the rows
     'euclid_norm_by_cols': ('loss_kernels.hpp', 'if (q.norm) sc /= static_cast<float>(q.rows);',
                             'if (q.norm) sc /= static_cast<float>(q.cols);'),
+    # the bf16x3 math mode (tests/test_gpu_bf3_shapes.py): each stays inside its request's workspace.
+    # The ring's re-load in the loop never fetches the last chunk: wrong from four chunks of 16 k on
+    'bf3_ring_reload_last_but_one': ('nt_core.hpp', 'dma(prev, (c + 2 < last) ? c + 2 : last);',
+                                     'dma(prev, (c + 2 < last - 1) ? c + 2 : last - 1);'),
+    # the step epilogue's pre-split state row: the odd unit of a pair without its lo half
+    'bf3_epilogue_odd_lo': ('gru_step_tile.hpp', 'const uint32_t lo = pack_bf16(hn[r] - f0, o1 - f1);',
+                            'const uint32_t lo = pack_bf16(hn[r] - f0, 0.f);'),
+    # the projection's ring launch runs past rows_split, over pre-split rows no step has written
+    'bf3_attn_ring_past_cut': ('gru.hip', 'const int64_t cut = job.rows_split < lo ? lo : (job.rows_split > hi ? hi : job.rows_split);',
+                               'const int64_t cut = hi;'),
+    # split_rows_kernel truncates the hi half instead of rounding it to nearest even
+    'bf3_split_rows_truncates': ('gru_rows.hpp', '\n    const uint32_t hi = pack_bf16(x0, x1);',
+                                 '\n    const uint32_t hi = (__float_as_uint(x0) >> 16) | (__float_as_uint(x1) & 0xffff0000u);'),
+    # the ring step skips the h phase of step 0: the caller's initial states enter through z h only
+    'bf3_h0_ignored': ('gru_step_tile.hpp', 'if (have_h) nt_phase_bf3_ring<', 'if (have_h && t > 0) nt_phase_bf3_ring<'),
+    # the 64-row workgroups of bf16x3 requests count towards the exact requests' tall-tile threshold
+    'bf3_tiled_wgs_counts_bf3': ('gru.hip', 'if (jobs[k].kind_count[t] > tiny_max_seqs() && !jobs[k].bf3)',
+                                 'if (jobs[k].kind_count[t] > tiny_max_seqs())'),
+}
+# mutants that change no result, with the reason: run and reported, but no test can kill them
+EQUIVALENT = {
+    'bf3_tiled_wgs_counts_bf3': 'moves an exact request between 64- and 128-row tiles, which give the same bits; the line is '
+                                'pinned by tests/test_bf3_shapes_cpu.py (fwd_shapes.TILED_WGS_ALSO)',
 }
 # the tests that must kill them (and pass on the product library)
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
           'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py',
-          'tests/test_gpu_loss_shapes.py', '-k',
+          'tests/test_gpu_loss_shapes.py', 'tests/test_gpu_bf3_shapes.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
           'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
-          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes']
+          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes or bf3_shape']
 
 
 def build(only=()):
@@ -161,7 +189,10 @@ def run(only=()):
     for l in res.stdout.splitlines():
       if 'Max absolute difference' in l or 'Mismatched elements' in l:
         print('      ', l.strip())
-  ok = results['product'][0] == 0 and all(results[m][1] for m in results if m != 'product')
+  for m in results:
+    if m in EQUIVALENT:
+      print('(%s: an equivalent mutant — %s)' % (m, EQUIVALENT[m]))
+  ok = results['product'][0] == 0 and all(results[m][1] for m in results if m != 'product' and m not in EQUIVALENT)
   print('mutation check:', 'every mutant killed, product green' if ok else 'HOLE: see above')
   return 0 if ok else 1
 
