@@ -1510,6 +1510,8 @@ int tune_in(Tunables& t, const char* name, int32_t value, int32_t* old_value) {
   };
   for (auto& e : table)
     if (strcmp(name, e.name) == 0) {
+      // (the one knob with a range: a scale below 1 would make cmhse_sim_rank_exact's tolerance invalid)
+      if (e.v == &t.rank_exact_tol_scale && value >= 0 && (value < 1 || value > (1 << 20))) return CMHSE_ERR_ARG;
       const int old = (value >= 0) ? e.v->exchange(value) : e.v->load();
       if (old_value) *old_value = old;
       if (value > 0 && (e.v == &t.chain_min_steps || e.v == &t.fwd_tail_min_steps || e.v == &t.bwd_tail_min_steps)) {

@@ -71,7 +71,8 @@ struct GruWs {
   X(chain_tall_min_wgs, 256)  /* 64-row workgroups per step from which a step chain uses 128-row tiles */ \
   X(pull_waves, 32)           /* single-wave workgroups of one cmhse_pull_steps launch (host -> HBM over PCIe) */ \
   X(tok_table, 1)             /* 1: a token-fed exact inference call with word-steps >= 4 x vocab projects the vocabulary once */ \
-  X(share_prefix, 1)          /* 1: the host glue pools a video's first caption from its paragraph's rows (cmhse_seq_batch.n_alias) */
+  X(share_prefix, 1)          /* 1: the host glue pools a video's first caption from its paragraph's rows (cmhse_seq_batch.n_alias) */ \
+  X(rank_exact_tol_scale, 1)  /* 1 .. 2^20: multiplies the tolerance of cmhse_sim_rank_exact (more pairs through float64, same results) */
 
 struct Tunables {
 #define CMHSE_TUNABLE_MEMBER_(name, dflt) std::atomic<int> name{dflt};

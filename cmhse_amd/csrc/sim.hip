@@ -9,6 +9,9 @@
 //   cmhse_sim_rank_labelled  the same ranking against any set of positives per query, any gallery
 //                         size: a threshold pass over the (query, positive) pairs in the place of the
 //                         diagonal pass, then the same counting pass without the excluded column.
+//   cmhse_sim_rank_exact  the ranking of the FLOAT64 scores of the same rows, as an interval [optimistic,
+//                         pessimistic]: the counting pass decides every comparison that the fp32 scores
+//                         provably decide and recomputes the others in float64 inside the tile.
 //   cmhse_cosine_sim      loss.cosine_sim       (/root/reference/loss.py:12-13): the stored-score GEMM,
 //                         which the training losses of loss.hip launch through sim_store.hpp
 //
@@ -35,7 +38,9 @@ constexpr int kSimSmallMax = 512;   // stored-score matrices up to this size use
 
 // kSimLabel: the counting pass of cmhse_sim_rank_labelled — kSimRank's, except that p.diag holds a
 // per-row threshold (the best positive's score) instead of the diagonal and no column is excluded.
-enum { kSimDiag = 0, kSimRank = 1, kSimStore = 2, kSimLabel = 3 };
+// kSimExact: the counting pass of cmhse_sim_rank_exact — kSimRank's with a per-row tolerance: two compares
+// per element, and the pairs neither decides go through dot64 (below) before the workgroup leaves.
+enum { kSimDiag = 0, kSimRank = 1, kSimStore = 2, kSimLabel = 3, kSimExact = 4 };
 
 struct SimParams {
   const float* A;  // [N, D]
@@ -50,7 +55,29 @@ struct SimParams {
   // scores of block b at scores + b * blk_stride, leading dimension = the block's size
   const int32_t* blk_off;
   int64_t blk_stride;
+  // kSimExact only (behind everything the other modes read)
+  const float* tol;             // [nrows] the certified half-width of "undecided" around diag[i]
+  const double* s64_diag;       // [nrows] dot64 of row i with its diagonal column
+  int32_t* ties;                // [nrows] resolved pairs whose float64 score EQUALS the diagonal's
+  int32_t* resolved;            // [nrows] pairs that went through dot64
 };
+
+// THE float64 score of two fp32 rows: every s64 of cmhse_sim_rank_exact — the diagonal's, an undecided
+// pair's, the squared norms of the tolerance — comes out of this one routine, so two pairs of bit-identical
+// rows have bit-identical scores whichever kernel asked.  One wave, all 64 lanes: lane l runs the chain
+// acc = fma(double(a[k]), double(b[k]), acc) over k = l, l + 64, ... ascending from acc = 0 (the product of
+// two fp32 values is exact in float64: one rounding per term), then the 64 partial sums are added in a
+// butterfly over lane distances 32, 16, 8, 4, 2, 1 (x + y is commutative, so every lane holds the same
+// bits).  Reads are coalesced (256 B per wave and step); the rows are L2-hot in the counting pass.
+__device__ __forceinline__ double dot64(const float* a, const float* b, int D, int lane) {
+  double acc = 0.0;
+  for (int k = lane; k < D; k += 64) acc = fma(static_cast<double>(a[k]), static_cast<double>(b[k]), acc);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  return acc;
+}
+
+constexpr int kExactWords = kSimBM * kSimBN / 32;   // bitmap of a tile's undecided pairs: 2 KB of LDS
 
 // TS = 32 x 32 blocks per wave in each direction: 2 = the 128 x 128 tile; 1 = a 64 x 64 tile for the
 // small matrices of the training losses (n = 32 ... ~130: ONE 128 x 128 workgroup there is a
@@ -87,7 +114,8 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
         (static_cast<uint64_t>(__builtin_amdgcn_s_getreg((31 << 11) | 20)) << 32);
   }
 #endif
-  constexpr bool COUNT = MODE == kSimRank || MODE == kSimLabel;   // the counting passes
+  constexpr bool COUNT = MODE == kSimRank || MODE == kSimLabel || MODE == kSimExact;   // the counting passes
+  static_assert(MODE != kSimExact || TS == 2, "the bitmap is laid out for the 128 x 128 tile");
   SimParams p = p_;
   if (p.blk_off != nullptr) {
     const int off = p.blk_off[blockIdx.y];
@@ -138,6 +166,8 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
   // they go through LDS once the tile buffers are free
   float my_diag = 0.f;
   if (COUNT && tid < BM) my_diag = (i0 + tid < p.nrows) ? p.diag[i0 + tid] : 0.f;
+  float my_tol = 0.f;
+  if (MODE == kSimExact && tid < BM) my_tol = (i0 + tid < p.nrows) ? p.tol[i0 + tid] : 0.f;
   SIM_MARK(1);
   SIM_CLOCK(5);
   nt_phase<BM, BN, TS, TS, TS, TS - 1, VEC>(smem, ar, av, br, bv, p.D, wm * 32 * TS, b_row0, acc);
@@ -149,8 +179,15 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
     // nothing: 404 / 407 us per launch)
     __syncthreads();                 // every wave has read its last fragments
     if (tid < BM) smem[tid] = my_diag;
+    if (MODE == kSimExact) {
+      if (tid < BM) smem[BM + tid] = my_tol;
+      if (tid == 0) smem[2 * BM + kExactWords] = 0.f;    // "some pair of this tile is undecided"
+    }
     __syncthreads();
   }
+  // kSimExact, behind the diagonals and tolerances: word 4 row + c holds the undecided pairs of tile row
+  // `row` and tile columns [32 c, 32 c + 32), bit = column; every word is written below, by one half-wave
+  unsigned* const s_amb = reinterpret_cast<unsigned*>(smem + 2 * BM);
 
 #pragma unroll
   for (int ms = 0; ms < TS; ++ms) {
@@ -181,6 +218,7 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
         // (profiles/r04_sim_kernel_trace.txt).  Same count, same key (ordered bits of the score,
         // then the smaller column), same atomics.
         const float dii = smem[li - i0];          // (0 for rows past the stripe: never counted)
+        const float tol = (MODE == kSimExact) ? smem[BM + li - i0] : 0.f;
         const bool hi = lane >= 32;
         int cnt = 0;
         unsigned ob[TS];
@@ -190,7 +228,22 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
           const int j = j0 + b_row0[ns] + acc_col(lane);
           const float v = acc[ms][ns][r];
           const bool valid = rok && j < p.M;
-          const unsigned long long gt = __ballot(valid && (MODE == kSimLabel || j != gi) && v > dii);
+          unsigned long long gt;
+          if (MODE == kSimExact) {
+            // surely above: fl(v - dii) > tol; surely below: fl(dii - v) = -fl(v - dii) > tol; else undecided
+            // (tol >= 0, possibly +inf: everything undecided; inputs finite, so the difference is no NaN)
+            const float diff = v - dii;
+            const bool mine = valid && j != gi;
+            gt = __ballot(mine && diff > tol);
+            const unsigned long long amb = __ballot(mine && fabsf(diff) <= tol);
+            if ((lane & 31) == 0) {
+              const unsigned w = hi ? static_cast<unsigned>(amb >> 32) : static_cast<unsigned>(amb);
+              s_amb[(li - i0) * 4 + (b_row0[ns] >> 5)] = w;
+              if (w != 0u) smem[2 * BM + kExactWords] = 1.f;
+            }
+          } else {
+            gt = __ballot(valid && (MODE == kSimLabel || j != gi) && v > dii);
+          }
           cnt += __popc(hi ? static_cast<unsigned>(gt >> 32) : static_cast<unsigned>(gt));
           ob[ns] = valid ? ordered_bits(v) : 0u;
           obmax = ob[ns] > obmax ? ob[ns] : obmax;
@@ -210,6 +263,38 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
         if (rok && (lane & 31) == 0) {
           if (cnt) atomicAdd(&p.rank[li], cnt);
           if (jbest >= 0) atomicMax(&p.top1key[li], bits_key(obmax, jbest));
+        }
+      }
+    }
+  }
+  if (MODE == kSimExact) {
+    // The resolve step.  The barrier and the test are workgroup-uniform (every thread of a workgroup that
+    // gets here reads the same LDS word), the loops are bounded by the 512 bitmap words and their 32 bits,
+    // and nothing waits on another workgroup.  Wave w takes the words w, w + 4, ...: the 32 columns of one
+    // tile row each; every set bit is one dot64 of that row with the bit's column, compared with the row's
+    // dot64 diagonal.  Integer atomics: the sums do not depend on who adds first.
+    __syncthreads();
+    if (smem[2 * BM + kExactWords] != 0.f) {
+      for (int w = wave; w < kExactWords; w += kThreads / 64) {
+        unsigned bits = __builtin_amdgcn_readfirstlane(s_amb[w]);
+        if (bits == 0u) continue;
+        const int li = i0 + (w >> 2);              // (< nrows: rows past the stripe set no bit)
+        const int jw = j0 + (w & 3) * 32;
+        const float* arow = p.A + static_cast<int64_t>(p.row0 + li) * p.D;
+        const double sii = p.s64_diag[li];
+        int above = 0, equal = 0, n = 0;
+        while (bits != 0u) {
+          const int c = __ffs(bits) - 1;           // (column jw + c < M: columns past the gallery set no bit)
+          bits &= bits - 1u;
+          const double s = dot64(arow, p.B + static_cast<int64_t>(jw + c) * p.D, p.D, lane);
+          above += s > sii;
+          equal += s == sii;
+          ++n;
+        }
+        if (lane == 0) {
+          if (above) atomicAdd(&p.rank[li], above);
+          if (equal) atomicAdd(&p.ties[li], equal);
+          atomicAdd(&p.resolved[li], n);
         }
       }
     }
@@ -316,6 +401,100 @@ __global__ void label_decode_kernel(const score_key_t* key, float* thr, int32_t*
   if (best_score) best_score[i] = key_score(k);
 }
 
+// ---------------------------------------------------------------------------------------------
+// cmhse_sim_rank_exact: the tolerance, the pre-pass and the last pass around sim_kernel<kSimExact>.
+//
+// The bound.  v(i,j) is the MFMA k-chain: D fused multiply-adds in fp32, one rounding each (unit roundoff
+// u = 2^-24), in an order that does not matter here.  With gamma_n(u) = n u / (1 - n u), the standard
+// bound of such a chain (Higham, Accuracy and Stability of Numerical Algorithms, section 3.1) is
+//   |v(i,j) - a_i . b_j| <= gamma_D(u) sum_k |a_ik b_jk| <= gamma_D(u) |a_i| |b_j|    (Cauchy-Schwarz)
+// as long as no step underflows.  fp32 subnormals are kept here (neither the operands nor the
+// accumulator of the MFMA flush), so a step whose result falls below 2^-126 is off by at most half a
+// subnormal step, 2^-150: D 2^-149 in all, added as an absolute term.  No other assumption is made on
+// small products; the inputs are assumed finite, and D < 2^24.
+// s64(i,j) is dot64: chains of at most ceil(D / 64) fused multiply-adds in float64 (u' = 2^-53; the
+// products are exact) and six more additions: |s64(i,j) - a_i . b_j| <= gamma_{ceil(D/64)+6}(u') |a_i| |b_j|,
+// taken here as (D / 64 + 8) 2^-53 (the denominator 1 - n u' is covered by the slack below).  So
+//   |v(i,j) - s64(i,j)| <= E_i = (gamma_D(u) + (D / 64 + 8) 2^-53) |a_i| max_j |b_j| + D 2^-149
+// for every column j, the diagonal included, and |fl(v(i,j) - v(i,i))| > 2 E_i / (1 - u) decides the sign
+// of s64(i,j) - s64(i,i) (the fp32 subtraction is off by a factor 1 + d, |d| <= u).  What is left is the
+// arithmetic of the tolerance itself: the norms are sqrt(dot64(x, x)), relative error below 2^-45 for
+// D < 2^24; the maximum over j is rounded UP to fp32 before its atomic max; the dozen float64 operations
+// below are off by 2^-53 each; the result, times the tunable rank_exact_tol_scale, is rounded UP to the
+// fp32 the kernel compares with.  All of that, 1 / (1 - u) included, lies far inside the factor 1 + 2^-18.
+// The value stays within 1 + 2^-11 of the textbook 2 D u |a| |b| up to D = 4096: nothing is given away.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ inline double exact_tolerance(int32_t D, double norm_a, double norm_b_max) {
+  const double du = static_cast<double>(D) * 0x1p-24;
+  if (!(du < 1.0)) return INFINITY;
+  const double gamma = du / (1.0 - du);
+  const double e64 = static_cast<double>(D / 64 + 8) * 0x1p-53;
+  const double e = (gamma + e64) * norm_a * norm_b_max + static_cast<double>(D) * 0x1p-149;
+  return 2.0 * e * (1.0 + 0x1p-18);
+}
+
+// the smallest fp32 that is not below x >= 0
+__device__ __forceinline__ float round_up_f32(double x) {
+  float f = static_cast<float>(x);
+  if (static_cast<double>(f) < x) f = __uint_as_float(__float_as_uint(f) + 1u);   // (f >= 0, finite)
+  return f;
+}
+
+struct ExactPreParams {
+  const float* A;            // [N, D]
+  const float* B;            // [M, D]
+  int32_t M, D, row0, nrows;
+  double* s64_diag;          // [nrows]
+  double* norm_a;            // [nrows]
+  unsigned* norm_b_max;      // the bits of the largest |b_j| (rounded up), zeroed; bits of floats >= 0 order as integers
+  int32_t* rank_lo;          // [nrows] the call's counters, zeroed here
+  int32_t* ties;
+  int32_t* resolved;
+  score_key_t* top1key;
+};
+
+// One wave per row: the nrows stripe rows first (diagonal score, norm, zeroed counters), then the M
+// gallery rows (norm into the maximum).
+__global__ __launch_bounds__(kThreads) void exact_pre_kernel(const ExactPreParams p) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6);
+  if (r < p.nrows) {
+    const float* a = p.A + (static_cast<int64_t>(p.row0) + r) * p.D;
+    const float* b = p.B + (static_cast<int64_t>(p.row0) + r) * p.D;
+    const double sii = dot64(a, b, p.D, lane);
+    const double na = sqrt(dot64(a, a, p.D, lane));
+    if (lane == 0) {
+      p.s64_diag[r] = sii;
+      p.norm_a[r] = na;
+      p.rank_lo[r] = 0;
+      p.ties[r] = 0;
+      p.resolved[r] = 0;
+      p.top1key[r] = 0ull;
+    }
+  } else if (r < static_cast<int64_t>(p.nrows) + p.M) {
+    const float* b = p.B + (r - p.nrows) * p.D;
+    const double nb = sqrt(dot64(b, b, p.D, lane));
+    if (lane == 0) atomicMax(p.norm_b_max, __float_as_uint(round_up_f32(nb)));
+  }
+}
+
+__global__ void exact_tol_kernel(const double* norm_a, const unsigned* norm_b_max, float* tol, int32_t D,
+                                 int32_t scale, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double nb = static_cast<double>(__uint_as_float(*norm_b_max));
+  tol[i] = round_up_f32(exact_tolerance(D, norm_a[i], nb) * static_cast<double>(scale));
+}
+
+// rank_hi arrives holding the ties of the resolved pairs
+__global__ void exact_finalize_kernel(const score_key_t* key, const int32_t* rank_lo, int32_t* rank_hi,
+                                      int32_t* top1, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  top1[i] = key_index(key[i]);
+  rank_hi[i] += rank_lo[i];
+}
+
 // The stored-score GEMM (sim_store.hpp): the one place that chooses its tile size.
 int launch_sim_store(const float* A, const float* B, int n, int m, int D, float* scores,
                      hipStream_t stream, const int32_t* blk_off, int n_blocks, int64_t blk_stride) {
@@ -413,6 +592,106 @@ extern "C" int cmhse_sim_rank(const float* A, const float* B, int32_t N, int32_t
                               void* workspace, size_t workspace_bytes, void* stream_) {
   return cmhse_sim_rank_ex(A, B, N, M, D, row0, nrows, rank, top1, workspace, workspace_bytes,
                            stream_, nullptr);
+}
+
+namespace {
+struct ExactWs {
+  size_t diag, top1key, s64_diag, norm_a, tol, norm_b_max, total;
+};
+ExactWs exact_ws(int32_t nrows) {
+  const size_t n = static_cast<size_t>(nrows);
+  ExactWs L;
+  size_t off = 0;
+  L.diag = off, off += align256(n * sizeof(float));
+  L.top1key = off, off += align256(n * sizeof(score_key_t));
+  L.s64_diag = off, off += align256(n * sizeof(double));
+  L.norm_a = off, off += align256(n * sizeof(double));
+  L.tol = off, off += align256(n * sizeof(float));
+  L.norm_b_max = off, off += 256;
+  L.total = off;
+  return L;
+}
+}  // namespace
+
+extern "C" size_t cmhse_sim_rank_exact_workspace(int32_t nrows) {
+  if (nrows <= 0) return 0;
+  return exact_ws(nrows).total;
+}
+
+extern "C" double cmhse_sim_rank_exact_tolerance(int32_t D, double norm_a, double norm_b_max) {
+  if (D <= 0 || !(norm_a >= 0.0) || !(norm_b_max >= 0.0)) return NAN;
+  return exact_tolerance(D, norm_a, norm_b_max);
+}
+
+extern "C" int cmhse_sim_rank_exact(const float* A, const float* B, int32_t N, int32_t M, int32_t D,
+                                    int32_t row0, int32_t nrows, int32_t* rank_lo, int32_t* rank_hi,
+                                    int32_t* top1, int32_t* resolved, void* workspace,
+                                    size_t workspace_bytes, void* stream_) {
+  if (!A || !B || !rank_lo || !rank_hi || !top1 || !resolved || !workspace) return CMHSE_ERR_ARG;
+  if (N <= 0 || M <= 0 || D <= 0 || row0 < 0 || nrows < 0 || static_cast<int64_t>(row0) + nrows > N)
+    return CMHSE_ERR_ARG;
+  if (static_cast<int64_t>(row0) + nrows > M) return CMHSE_ERR_ARG;  // diagonal d[i][i] must exist
+  if (nrows == 0) return CMHSE_OK;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
+      workspace_bytes < cmhse_sim_rank_exact_workspace(nrows))
+    return CMHSE_ERR_WORKSPACE;
+  if (D >= (1 << 24)) return CMHSE_ERR_UNSUPPORTED;   // (the bound needs D u < 1)
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const ExactWs L = exact_ws(nrows);
+  char* const ws = static_cast<char*>(workspace);
+  SimParams p;
+  p.A = A;
+  p.B = B;
+  p.N = N;
+  p.M = M;
+  p.D = D;
+  p.row0 = row0;
+  p.nrows = nrows;
+  p.n_tiles = (M + kSimBN - 1) / kSimBN;
+  p.diag = reinterpret_cast<float*>(ws + L.diag);
+  p.top1key = reinterpret_cast<score_key_t*>(ws + L.top1key);
+  p.rank = rank_lo;
+  p.scores = nullptr;
+  p.blk_off = nullptr;
+  p.blk_stride = 0;
+  p.tol = reinterpret_cast<float*>(ws + L.tol);
+  p.s64_diag = reinterpret_cast<double*>(ws + L.s64_diag);
+  p.ties = rank_hi;
+  p.resolved = resolved;
+  const int m_tiles = (nrows + kSimBM - 1) / kSimBM;
+  const XcdDeal deal = xcd_deal(m_tiles, p.n_tiles);
+  p.group = deal.group;
+  if (deal.blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  ExactPreParams q;
+  q.A = A;
+  q.B = B;
+  q.M = M;
+  q.D = D;
+  q.row0 = row0;
+  q.nrows = nrows;
+  q.s64_diag = reinterpret_cast<double*>(ws + L.s64_diag);
+  q.norm_a = reinterpret_cast<double*>(ws + L.norm_a);
+  q.norm_b_max = reinterpret_cast<unsigned*>(ws + L.norm_b_max);
+  q.rank_lo = rank_lo;
+  q.ties = rank_hi;
+  q.resolved = resolved;
+  q.top1key = p.top1key;
+  const int32_t scale = tunables().rank_exact_tol_scale.load(std::memory_order_relaxed);
+  if (hipMemsetAsync(q.norm_b_max, 0, sizeof(unsigned), stream) != hipSuccess) return CMHSE_ERR_LAUNCH;
+  const int64_t pre_rows = static_cast<int64_t>(nrows) + M;
+  hipLaunchKernelGGL(exact_pre_kernel, dim3(static_cast<unsigned>((pre_rows + kThreads / 64 - 1) / (kThreads / 64))),
+                     dim3(kThreads), 0, stream, q);
+  hipLaunchKernelGGL(exact_tol_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream, q.norm_a,
+                     q.norm_b_max, reinterpret_cast<float*>(ws + L.tol), D, scale, nrows);
+  const size_t smem = TileSmem<kSimBM, kSimBN>::kBytes;
+  int rc = launch_tiles(sim_kernel<kSimDiag, true>, sim_kernel<kSimDiag, false>, D, dim3(m_tiles), smem, stream, p);
+  if (rc != CMHSE_OK) return rc;
+  rc = launch_tiles(sim_kernel<kSimExact, true>, sim_kernel<kSimExact, false>, D,
+                    dim3(static_cast<unsigned>(deal.blocks)), smem, stream, p);
+  if (rc != CMHSE_OK) return rc;
+  hipLaunchKernelGGL(exact_finalize_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream, p.top1key,
+                     rank_lo, rank_hi, top1, nrows);
+  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }
 
 extern "C" size_t cmhse_sim_rank_labelled_workspace(int32_t nrows, int32_t n_pairs) {

@@ -1200,6 +1200,41 @@ def i2t_t2i_labelled(images, captions, pairs):
           (report_from_ranks(host[2]), host[3], host[2]))
 
 
+def i2t_t2i_exact(images, captions, ties='optimistic'):
+  """i2t_t2i on the ranks of the FLOAT64 scores of the two matrices, certified (ops.sim_rank_exact):
+  independent of summation order, tile shape and machine, where the fp32 ranks of i2t / t2i differ from
+  a float64 ranking of the same embeddings on about one row in a few thousand.  Returns
+  ((report, top1, ranks) image -> caption, the same caption -> image, info), the first two in i2t_t2i's
+  format; `ranks` is rank_lo for ties='optimistic' (a gallery row that ties the positive exactly is not
+  counted: i2t's rule) and rank_hi for ties='pessimistic' (it is: a collapsed model reports the last
+  rank, not the first).  info = {'i2t': d, 't2i': d, 'resolved': total}, each d with 'report_lo',
+  'report_hi' (report_from_ranks of the two vectors), 'tied_rows' (the rows with rank_lo < rank_hi) and
+  'resolved' (the pairs that went through float64).  top1 is sim_rank's, not certified.  NumPy arrays or
+  GPU tensors; one device-to-host copy; GPU tensors in: top1 and ranks stay int32 device tensors.  The
+  ranking cache i2t / t2i serve from is neither read nor changed."""
+  if ties not in ('optimistic', 'pessimistic'):
+    raise ValueError("ties must be 'optimistic' or 'pessimistic', got %r" % (ties,))
+  on_device = isinstance(images, torch.Tensor) and images.is_cuda
+  v = _as_device(images)
+  p = _as_device(captions, v.device)
+  out_i = ops.sim_rank_exact(v, p)
+  out_t = ops.sim_rank_exact(p, v)
+  n, m = out_i[0].numel(), out_t[0].numel()
+  # (the two sides may differ in length: one flat vector, cut on the host)
+  flat = torch.cat(list(out_i) + list(out_t)).cpu().numpy()
+  host_i = [x.astype(numpy.float64) for x in numpy.split(flat[:4 * n], 4)] if n else [numpy.zeros(0)] * 4
+  host_t = [x.astype(numpy.float64) for x in numpy.split(flat[4 * n:], 4)] if m else [numpy.zeros(0)] * 4
+  pick = 0 if ties == 'optimistic' else 1
+  info, sides = {}, []
+  for name, host, dev in (('i2t', host_i, out_i), ('t2i', host_t, out_t)):
+    info[name] = dict(report_lo=report_from_ranks(host[0]), report_hi=report_from_ranks(host[1]),
+                      tied_rows=numpy.flatnonzero(host[0] < host[1]), resolved=int(host[3].sum()))
+    report = info[name]['report_lo' if pick == 0 else 'report_hi']
+    sides.append((report, dev[2], dev[pick]) if on_device else (report, host[2], host[pick]))
+  info['resolved'] = info['i2t']['resolved'] + info['t2i']['resolved']
+  return sides[0], sides[1], info
+
+
 def _rank_report(queries, gallery):
   rank, top1 = ops.sim_rank(_as_device(queries), _as_device(gallery))
   ranks = rank.cpu().numpy().astype(numpy.float64)      # the reference stores ranks in float64

@@ -95,7 +95,8 @@ def tune(name, value=-1):
   are initialised from.  Names: tiny_max_seqs, mid_max_seqs, mid_units, mid_waves,
   tall_tile_min_wgs, mid_tall_min_seqs, bwd_mid_max_seqs, bwd_split_min_seqs, bwd_tail_min_steps,
   fwd_tail_min_steps, bwd_chunk_rows, xproj_chunk_rows, tn_rows_bm, chain_min_steps, early_xproj,
-  chain_tall_min_wgs, pull_waves, resident_timeout_ms, tok_table, share_prefix (include/cmhse_hip.h)."""
+  chain_tall_min_wgs, pull_waves, resident_timeout_ms, tok_table, share_prefix, rank_exact_tol_scale
+  (include/cmhse_hip.h)."""
   ctx = TuneContext.current()
   if ctx is not None:
     return ctx.tune(name, value)
@@ -846,6 +847,33 @@ def sim_rank(a, b, row0=0, nrows=None):
                              top1.data_ptr(), ws.data_ptr(), ws_bytes, _stream(), timer)
   _lib.check(rc, 'cmhse_sim_rank')
   return rank, top1
+
+
+def sim_rank_exact(a, b, row0=0, nrows=None):
+  """The ranks of the FLOAT64 scores of the stripe [row0, row0+nrows) of a @ b.T, certified
+  (cmhse_sim_rank_exact): int32 device tensors (rank_lo, rank_hi, top1, resolved) on the current stream.
+  rank_lo counts the columns strictly above the diagonal (sim_rank's rule), rank_hi those at or above it
+  (they differ only on exact float64 ties: bit-identical gallery rows); top1 is sim_rank's, not
+  certified; resolved the pairs of each row that fp32 could not decide and float64 did.  The result
+  depends on neither summation order, tile shape nor machine."""
+  lib = _lib.load()
+  a = _f32c(a, 'a')
+  b = _f32c(b, 'b')
+  N, D = a.shape
+  M = b.shape[0]
+  if b.shape[1] != D:
+    raise ValueError('embedding widths differ')
+  if nrows is None:
+    nrows = N - row0
+  out = torch.empty(4, max(nrows, 0), dtype=torch.int32, device=a.device)
+  if nrows != 0:
+    ws_bytes = lib.cmhse_sim_rank_exact_workspace(nrows)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    rc = lib.cmhse_sim_rank_exact(a.data_ptr(), b.data_ptr(), N, M, D, row0, nrows, out[0].data_ptr(),
+                                  out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), ws.data_ptr(),
+                                  ws_bytes, _stream())
+    _lib.check(rc, 'cmhse_sim_rank_exact')
+  return out[0], out[1], out[2], out[3]
 
 
 def sim_topk(queries, gallery, k, row0=0, nrows=None):

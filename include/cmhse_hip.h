@@ -382,6 +382,50 @@ int cmhse_sim_rank_labelled(const float* A, const float* B, int32_t N, int32_t M
                             int32_t* best_pos /*[nrows]*/, float* best_score /*[nrows] or NULL*/,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* Certified ranking: the ranks of the FLOAT64 scores of the same fp32 rows, at about the cost of
+ * cmhse_sim_rank.  A [N,D], B [M,D], the stripe [row0, row0+nrows) with row0 + nrows <= M (the diagonal
+ * convention of cmhse_sim_rank).  s64(i,j) is the float64 dot product of the fp32 rows i of A and j of B:
+ * exact products, summed in ONE fixed order by ONE routine that serves every pair, (i,i) included (one
+ * wave: lane l adds the terms k = l, l + 64, ... ascending by fused multiply-add from 0, then the 64
+ * partial sums are added pairwise over lane distances 32, 16, 8, 4, 2, 1).  All outputs int32 [nrows]:
+ *   rank_lo[i - row0]  = #{ j != i : s64(i,j) >  s64(i,i) }   the optimistic rule of cmhse_sim_rank, on
+ *                        the float64 scores;
+ *   rank_hi[i - row0]  = #{ j != i : s64(i,j) >= s64(i,i) }   the pessimistic rank: above rank_lo only on
+ *                        exact float64 ties, which bit-identical gallery rows produce (a collapsed model
+ *                        has rank_lo 0 and rank_hi M - 1 everywhere);
+ *   top1[i - row0]     = cmhse_sim_rank's, by its fp32 rule, unchanged and NOT certified (certifying the
+ *                        arg-max needs the row maximum before the pass);
+ *   resolved[i - row0] = the pairs of row i that went through float64: a diagnostic, deterministic
+ *                        because the classification is.
+ * How: the counting pass of cmhse_sim_rank with a per-row tolerance tol_i = 2 E_i, where E_i bounds
+ * |v(i,j) - s64(i,j)| for the fp32 MFMA score v and every j (the fused-multiply-add chain bound
+ * gamma_D |a_i| max_j |b_j|, gamma_D = D u / (1 - D u), u = 2^-24, plus the float64 routine's own error and
+ * the rounding of the norm and tolerance arithmetic; derived in sim.hip).  v(i,j) - v(i,i) > tol_i: surely
+ * above, counted in both ranks; v(i,i) - v(i,j) > tol_i: surely below; anything else is recomputed as
+ * s64(i,j) and compared with s64(i,i), inside the tile that found it (no list of pairs, no capacity,
+ * no second pass).
+ * Properties: the results do not depend on the tolerance as long as it is valid (the tunable
+ * "rank_exact_tol_scale" only moves `resolved`), nor on tiling or scheduling (integer counts; one k order
+ * per routine); row stripes concatenate bit for bit into the whole call; the math mode does not matter
+ * (scoring is exact fp32 whatever the mode, as everywhere else).  Inputs are assumed finite; D < 2^24
+ * (CMHSE_ERR_UNSUPPORTED otherwise).
+ * cmhse_sim_rank_exact_workspace(nrows) is a function of nrows alone (0 for nrows <= 0; about 32 bytes a
+ * row).  Errors as cmhse_sim_rank's, before anything is launched: CMHSE_ERR_ARG for a null pointer, N, M or
+ * D <= 0, a stripe outside [0, N] or row0 + nrows > M; CMHSE_ERR_WORKSPACE for a workspace that is
+ * unaligned (256 bytes) or too small.  nrows == 0: nothing is launched.
+ * Cost: cmhse_sim_rank's two passes, one wave per row of the stripe and of B in front (norms, s64(i,i)),
+ * two small launches, and one wave-wide float64 dot product per undecided pair.
+ *
+ * cmhse_sim_rank_exact_tolerance(D, |a_i|, max_j |b_j|): tol_i as the kernel computes it (before the
+ * tunable's factor and the rounding up to fp32); host-only, no GPU.  NaN for D <= 0 or a negative norm,
+ * +inf for D >= 2^24. */
+size_t cmhse_sim_rank_exact_workspace(int32_t nrows);
+double cmhse_sim_rank_exact_tolerance(int32_t D, double norm_a, double norm_b_max);
+int cmhse_sim_rank_exact(const float* A, const float* B, int32_t N, int32_t M, int32_t D, int32_t row0,
+                         int32_t nrows, int32_t* rank_lo /*[nrows]*/, int32_t* rank_hi /*[nrows]*/,
+                         int32_t* top1 /*[nrows]*/, int32_t* resolved /*[nrows]*/, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* Group-wise video <-> paragraph scores and ranking from the low-level rows (the score
  * GroupWiseContrastiveLoss trains on, loss.py:26-41; upstream's validate() has its evaluation
  * commented out, train.py:228-244).  clips [Nc, D] and caps [Ns, D] are encode_data's clip and
@@ -711,6 +755,10 @@ int cmhse_timer_tiled(void* timer, float* ms_host, double* flops_host, double* b
  *                             tokens are a prefix of its paragraph's (cmhse_tok_prefix_check) and pools it
  *                             from the paragraph's rows (cmhse_seq_batch.n_alias); 0 = encode every caption
  *                             (results identical)
+ *   "rank_exact_tol_scale" 1  integer in [1, 2^20] (anything else: CMHSE_ERR_ARG) that multiplies the
+ *                             tolerance of cmhse_sim_rank_exact: more pairs go through float64 (`resolved`
+ *                             grows), every other output stays bit for bit; at 2^20 every pair of an input
+ *                             with D >= 16 does (tests: the float64 path ranks the whole matrix)
  *   "multi_step_off"       0  (not a crossover, and per DEVICE rather than per context) 1 while the
  *                             multi-step kernels are switched off on the calling thread's current device
  *                             after an acknowledged timeout (cmhse_async_status below); readable, and
