@@ -9,6 +9,7 @@ import torch
 
 from conftest import EMB_TOL, assert_emb_close, load_golden, golden_state_dicts, golden_batches  # noqa: F401
 
+import bwd_side_shapes
 from gpu_common import *  # noqa: F401,F403,E402
 from gpu_common import (_blas_threads, _check_train_step_vs_oracle, _full_opt, _nccl_worker, _np_batches,  # noqa: F401,E402
                         _np_state_dicts, _plan_setup, _RecordForward, _robust_rank_rows)
@@ -117,18 +118,15 @@ def test_tall_mid_step_tile_is_bit_identical(dev, tune):
       assert torch.equal(a, b), n_seq
 
 
-@pytest.mark.parametrize('cls,pool,I,H,S,T', [
-    ('Seq2Seq', 'seq2seq', 24, 64, 37, 9),        # 3H = 192: one tall tile, N < 128
-    ('Attention', 'attention', 200, 128, 150, 7),   # 3H = 384: two tall tiles; rows split into parts
-    ('Maxout', 'maxout', 36, 40, 21, 5),          # 3H = 120: a tall tile forced onto a ragged M
-    ('Seq2Seq', 'seq2seq', 130, 192, 300, 4),     # N = 130: a second column tile of 2; > 1024 rows
-])
+@pytest.mark.parametrize('cls,pool,I,H,S,T', bwd_side_shapes.TALL_TILE_CASES)
 def test_weight_gradient_tall_tile_vs_small_tile(dev, oracle, tune, cls, pool, I, H, S, T):
   """The weight-gradient products (gemm_tn_rows_kernel, tn_rows.hpp) on their 192-row tile (each
   wave 96 x 64 of C, two workgroups per CU) against the 128-row tile: every gradient equal to fp32
   rounding (the row split into parts is chosen per tile count, so the order of the partial sums may
   differ), each bitwise reproducible, and against the float64 oracle.  Ragged M (3H = 120 on a
-  192-row tile), N below and just above a column tile, row counts that are not a multiple of 16."""
+  192-row tile), N below and just above a column tile, row counts that are not a multiple of 16.
+  (The table, and the proof of its comments from the launch rule: tests/bwd_side_shapes.py,
+  tests/test_bwd_side_shapes_cpu.py.)"""
   from cmhse_amd import layers
   rng = np.random.RandomState(5 + H + S)
   torch.manual_seed(9)
@@ -138,8 +136,7 @@ def test_weight_gradient_tall_tile_vs_small_tile(dev, oracle, tune, cls, pool, I
     layer.rnn.bias_hh_l0.normal_(0, 0.1)
   sd = {'rnn.' + k: v.detach().numpy().astype(np.float64) for k, v in layer.state_dict().items()}
   layer = layer.to(dev)
-  lens = rng.randint(1, T + 1, size=S)
-  lens[0] = T
+  lens = bwd_side_shapes.tall_tile_lens(rng, S, T)
   x = np.zeros((S, T, I), dtype=np.float32)
   for i, l in enumerate(lens):
     x[i, :l] = rng.standard_normal((l, I))
@@ -164,18 +161,20 @@ def test_weight_gradient_tall_tile_vs_small_tile(dev, oracle, tune, cls, pool, I
     grad_close(got.cpu().numpy(), grads['rnn.' + pn], pool + ' ' + pn)
 
 
-@pytest.mark.parametrize('pool,cls', [('attention', 'Attention'), ('maxout', 'Maxout')])
+@pytest.mark.parametrize('pool,cls', bwd_side_shapes.TIME_CHUNK_CASES)
 def test_weight_gradients_in_time_chunks_beside_the_chain(dev, oracle, pool, cls, monkeypatch, tune):
   """The weight-gradient products (gemm_tn_rows_kernel) of a batch long enough to be taken in
   several chunks of time steps (sum T ~ 3.5 k packed rows: chunks close every >= 1024 rows, the
-  last one mid-tile), with widths that are not tile multiples (3H = 216 rows of C, I = 36) and so
-  few tiles that every launch is row-split (parts + ordered reduce): every gradient against the
+  chunk of the last steps and the one after it ending mid-tile), with widths that are not tile
+  multiples (3H = 216 rows of C, I = 36) and so few tiles that every launch is row-split (parts + ordered reduce): every gradient against the
   float64 oracle; bit-identical with the products on the chain's own stream instead of the side
-  stream; and bitwise reproducible from run to run (no atomics on this path)."""
+  stream; and bitwise reproducible from run to run (no atomics on this path).  (The table, and the
+  proof of these claims from the launch rule: tests/bwd_side_shapes.py,
+  tests/test_bwd_side_shapes_cpu.py.)"""
   from cmhse_amd import layers, ops
-  tune(bwd_chunk_rows=1024)      # (default 2048: this batch would be two chunks)
+  tune(bwd_chunk_rows=bwd_side_shapes.TIME_CHUNK_ROWS)      # (1024; default 2048: this batch would be two chunks)
   rng = np.random.RandomState(77)
-  S, T, I, H = 330, 14, 36, 72
+  S, T, I, H = bwd_side_shapes.TIME_CHUNK_SHAPE      # 330, 14, 36, 72
   torch.manual_seed(8)
   layer = getattr(layers, cls)(I, H)
   with torch.no_grad():
@@ -183,9 +182,7 @@ def test_weight_gradients_in_time_chunks_beside_the_chain(dev, oracle, pool, cls
     layer.rnn.bias_hh_l0.normal_(0, 0.1)
   sd = {'rnn.' + k: v.detach().numpy().astype(np.float64) for k, v in layer.state_dict().items()}
   layer = layer.to(dev)
-  lens = rng.randint(1, T + 1, size=S)
-  lens[:200] = rng.randint(T - 2, T + 1, size=200)
-  lens[0] = T
+  lens = bwd_side_shapes.time_chunk_lens(rng, S, T)
   assert lens.sum() > 3 * 1024
   x = np.zeros((S, T, I), dtype=np.float32)
   for i, l in enumerate(lens):

@@ -30,6 +30,10 @@ Mutants:
                  the bf16x3 math mode (killed by tests/test_gpu_bf3_shapes.py — the last one changes the
                  exact neighbour's tile height only, which no result can show:
                  profiles/bf3_shapes_mutation_check.txt)
+  side_reduce_two_segments, side_reduce_ignores_add, side_tn_reduce_ignores_accumulate, side_attn_du_no_tanh,
+  side_colsum_first_slab, side_pool_all_negated
+                 what the backward launches beside the BPTT chain (killed by tests/test_gpu_bwd_side_shapes.py;
+                 which of them an older test catches: profiles/bwd_side_mutation_check.txt)
 """
 import os
 import shutil
@@ -122,6 +126,23 @@ MUTANTS = {
     # the 64-row workgroups of bf16x3 requests count towards the exact requests' tall-tile threshold
     'bf3_tiled_wgs_counts_bf3': ('gru.hip', 'if (jobs[k].kind_count[t] > tiny_max_seqs() && !jobs[k].bf3)',
                                  'if (jobs[k].kind_count[t] > tiny_max_seqs())'),
+    # what cmhse_gru_pool_bwd launches beside the chain (tests/test_gpu_bwd_side_shapes.py): value-only edits as above.
+    # The ordered split-K reduce adds two segments at most: wrong from three segments (K >= 768) on
+    'side_reduce_two_segments': ('bwd_pool_kernels.hpp', 'for (int y = 0; y < splits; ++y) s += part[(static_cast<int64_t>(y) * M + m) * N + n];',
+                                 'for (int y = 0; y < splits && y < 2; ++y) s += part[(static_cast<int64_t>(y) * M + m) * N + n];'),
+    # ... and stores where the attention backward's dpool += du . W_lin must add: the pooling gradient a g is lost
+    'side_reduce_ignores_add': ('bwd_pool_kernels.hpp', 'dst[n] = add ? dst[n] + s : s;', 'dst[n] = s;'),
+    # the weight-gradient row split's reduce stores into C on a later chunk: the chunks before it are lost
+    'side_tn_reduce_ignores_accumulate': ('tn_rows.hpp', '*dst = q.accumulate ? (*dst + s) : s;', '*dst = s;'),
+    # du without the tanh's 1 - v^2
+    'side_attn_du_no_tanh': ('bwd_pool_kernels.hpp', 'du[p * H + n] = d * w_att[n] * (1.0f - tv * tv);',
+                             'du[p * H + n] = d * w_att[n];'),
+    # d att_w from the first slab of 512 packed rows only
+    'side_colsum_first_slab': ('bwd_pool_kernels.hpp', 'for (int i = 0; i < slabs; ++i) s += part[static_cast<int64_t>(i) * cols + c];',
+                               'for (int i = 0; i < slabs && i < 1; ++i) s += part[static_cast<int64_t>(i) * cols + c];'),
+    # all-states pooling hands the chain the negated output gradient
+    'side_pool_all_negated': ('bwd_pool_kernels.hpp', 'for (int u = threadIdx.x; u < q.H; u += kThreads) d[u] = g[u];',
+                              'for (int u = threadIdx.x; u < q.H; u += kThreads) d[u] = -g[u];'),
 }
 # mutants that change no result, with the reason: run and reported, but no test can kill them
 EQUIVALENT = {
@@ -131,10 +152,10 @@ EQUIVALENT = {
 # the tests that must kill them (and pass on the product library)
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
           'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py',
-          'tests/test_gpu_loss_shapes.py', 'tests/test_gpu_bf3_shapes.py', '-k',
+          'tests/test_gpu_loss_shapes.py', 'tests/test_gpu_bf3_shapes.py', 'tests/test_gpu_bwd_side_shapes.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
           'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
-          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes or bf3_shape']
+          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes or bf3_shape or bwd_side_shape']
 
 
 def build(only=()):
