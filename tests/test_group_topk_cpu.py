@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from score_shapes import qcap      # group.hip gt_qcap restated: query groups per query tile at K
+
 HDR = 8
 P2V, V2P = 0, 1
 ERR_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -4
@@ -16,16 +18,6 @@ ERR_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -4
 def lib():
   from cmhse_amd import _lib
   return _lib.load()
-
-
-def qcap(K):
-  """Query groups per query tile at K (group.hip: gt_qcap): two workgroups' LDS per CU of 160 KB, or
-  one past K = 72; the fixed part is the 40 KB tile buffers and four 128-key candidate buffers."""
-  fixed, per_q = 40960 + 4096, 8 * K + 4 * 129
-  q = (81920 - fixed) // per_q // 8 * 8
-  if q < 32:
-    q = (163840 - fixed) // per_q // 8 * 8
-  return min(q, 64)
 
 
 def _offsets(counts):

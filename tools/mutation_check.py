@@ -34,6 +34,11 @@ Mutants:
   side_colsum_first_slab, side_pool_all_negated
                  what the backward launches beside the BPTT chain (killed by tests/test_gpu_bwd_side_shapes.py;
                  which of them an older test catches: profiles/bwd_side_mutation_check.txt)
+  score_deal_tile_g4, score_count_plain_order_swapped, score_group_plain_order_even_columns, score_topk_panel_even_split,
+  score_gtopk_panel_even_split, score_topk_list_rezeroed_per_tile, score_gtopk_list_rezeroed_per_tile,
+  score_merge_list_not_shifted
+                 the tile deal and the panel walk of the scoring kernels (killed by tests/test_gpu_score_shapes.py;
+                 which of them an older test catches: profiles/score_shapes_mutation_check.txt)
 """
 import os
 import shutil
@@ -143,6 +148,33 @@ MUTANTS = {
     # all-states pooling hands the chain the negated output gradient
     'side_pool_all_negated': ('bwd_pool_kernels.hpp', 'for (int u = threadIdx.x; u < q.H; u += kThreads) d[u] = g[u];',
                               'for (int u = threadIdx.x; u < q.H; u += kThreads) d[u] = -g[u];'),
+    # the tile deal and the panel walk of the scoring kernels (tests/test_gpu_score_shapes.py): index- or value-only
+    # edits, each inside the buffers its launch owns, no barrier added or moved.
+    # xcd_deal_tile splits a block's group index by 4 whatever G is: wrong for G = 2 and 3 (a row tile past the last
+    # one falls into the callers' padding return)
+    'score_deal_tile_g4': ('score_tile.hpp', 'const int Q = (q / G) * 8 + x;\n  return {G * (Q / col_tiles) + (q % G), Q % col_tiles};',
+                           'const int Q = (q / 4) * 8 + x;\n  return {G * (Q / col_tiles) + (q % 4), Q % col_tiles};'),
+    # the plain order of the counting passes (G = 0) swaps row and column tile past the first row of tiles
+    'score_count_plain_order_swapped': ('sim.hip', '    i0 = (blockIdx.x / p.n_tiles) * BM;\n  }',
+                                        '    i0 = (blockIdx.x / p.n_tiles) * BM;\n    if (COUNT && blockIdx.x >= static_cast<unsigned>(p.n_tiles)) {\n'
+                                        '      j0 = (blockIdx.x / p.n_tiles) * BN;\n      i0 = (blockIdx.x % p.n_tiles) * BM;\n    }\n  }'),
+    # the plain order of group_sim_kernel (G = 0) visits the even column tiles only
+    'score_group_plain_order_even_columns': ('group.hip', '    ct = blockIdx.x % p.col_tiles;', '    ct = (blockIdx.x % p.col_tiles) & ~1;'),
+    # the panels of the top-K select kernels hold col_tiles / panels tiles each: the remainder's tiles are never visited
+    'score_topk_panel_even_split': ('topk.hip', 'static_cast<int>(static_cast<int64_t>(panel) * p.col_tiles / p.panels);\n'
+                                    '  const int t_end = static_cast<int>(static_cast<int64_t>(panel + 1) * p.col_tiles / p.panels);',
+                                    'panel * (p.col_tiles / p.panels);\n  const int t_end = (panel + 1) * (p.col_tiles / p.panels);'),
+    'score_gtopk_panel_even_split': ('group.hip', 'static_cast<int>(static_cast<int64_t>(panel) * p.g_tiles / p.panels);\n'
+                                     '  const int t_end = static_cast<int>(static_cast<int64_t>(panel + 1) * p.g_tiles / p.panels);',
+                                     'panel * (p.g_tiles / p.panels);\n  const int t_end = (panel + 1) * (p.g_tiles / p.panels);'),
+    # the select kernels forget a row's running list at every tile: a panel keeps its last tile only
+    'score_topk_list_rezeroed_per_tile': ('topk.hip', 'score_key_t* lst = lists + row * K;',
+                                          'score_key_t* lst = lists + row * K;\n      for (int e = lane; e < K; e += 64) lst[e] = 0ull;'),
+    'score_gtopk_list_rezeroed_per_tile': ('group.hip', 'score_key_t* lst = lists + qi * K;',
+                                           'score_key_t* lst = lists + qi * K;\n      for (int e = lane; e < K; e += 64) lst[e] = 0ull;'),
+    # wave_merge leaves the list entries where they were: harmless into an empty list, wrong into a warm one
+    'score_merge_list_not_shifted': ('topk_lists.hpp', 'if (e < K && e + lr[h] < K) lst[e + lr[h]] = lv[h];',
+                                     'if (e < K && e + lr[h] < K) lst[e] = lv[h];'),
 }
 # mutants that change no result, with the reason: run and reported, but no test can kill them
 EQUIVALENT = {
@@ -152,10 +184,12 @@ EQUIVALENT = {
 # the tests that must kill them (and pass on the product library)
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
           'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py',
-          'tests/test_gpu_loss_shapes.py', 'tests/test_gpu_bf3_shapes.py', 'tests/test_gpu_bwd_side_shapes.py', '-k',
+          'tests/test_gpu_loss_shapes.py', 'tests/test_gpu_bf3_shapes.py', 'tests/test_gpu_bwd_side_shapes.py',
+          'tests/test_gpu_score_shapes.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
           'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
-          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes or bf3_shape or bwd_side_shape']
+          'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes or bf3_shape or bwd_side_shape or '
+          'score_shape']
 
 
 def build(only=()):
