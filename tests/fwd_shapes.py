@@ -162,14 +162,15 @@ def _tiled64_grid(H, S_t):
   return -(-H // GRU_BU) * -(-S_t // 64)
 
 
-def call_steps(jobs, knobs=None, tail_stream=False, side_streams=True, bf3=False):
+def call_steps(jobs, knobs=None, tail_stream=False, side_streams=True, bf3=False, attn=False):
   """launch_steps of one call.  `tail_stream`: the call has a side stream (ops passes one for two or
   more requests); `side_streams`: a training request gets its companion stream (ops.side_stream);
   `bf3`: the call runs in the bf16x3 math mode.  Returns, per request, a list of the launches that
   serve it: dicts with `kind` ('step', 'chain', 'tail', 'xproj'), the steps `ts` and `tag`, plus the
   pool modes its epilogue ran with; a 'step' launch also names the requests that share it (`group`).
   With `bf3`, the launches of the attention projection follow (`kind` 'attn': the rows [lo, hi), the
-  `cut`, `partial`), and every list carries the request's `bf3` flag and `rows_split`."""
+  `cut`, `partial`), and every list carries the request's `bf3` flag and `rows_split`; `attn` lists
+  them for an exact call too (tests/long_shapes.py: a partial launch, then a final one)."""
   k = dict(KNOBS, **(knobs or {}))
   jobs = [_prepare(j, k, bf3) for j in jobs]
   n = len(jobs)
@@ -264,8 +265,8 @@ def call_steps(jobs, knobs=None, tail_stream=False, side_streams=True, bf3=False
       group = [q for q in range(n) if not done[q] and t >= jobs[q]['chain_until'] and shape[q] == shape[m] and
                js[q] == js[m]]
       out[m].append(dict(kind='step', ts=[t], tag=tag, shape=shape[m], group=group))
-    _early_attention(jobs, t, Tmax, js, side, fork, out if bf3 else None, k)
-  if bf3:
+    _early_attention(jobs, t, Tmax, js, side, fork, out if (bf3 or attn) else None, k)
+  if bf3 or attn:
     for m, j in enumerate(jobs):
       if j['pool'] == 'ATTN' and not j['pooled']:
         _attention(j, out[m], j['sum_T'], True, k)

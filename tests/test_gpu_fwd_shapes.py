@@ -115,6 +115,10 @@ def _run_inference(jobs, layers_, data, dev, tail_stream):
       req['h0_ptrs'] = ops.padded_row_ptrs(ht)
     if j['plan'] is not None:
       req['step_plan'] = np.asarray(j['plan'], dtype=np.int32)
+    if j.get('aliases'):      # prefix aliases (src, len): output rows S, S + 1, ... behind the request's own
+      src, n = (np.asarray(a, dtype=np.int64) for a in zip(*j['aliases']))
+      S = len(lens)
+      req.update(out_rows=np.arange(S), aliases=(src, n, S + np.arange(len(src))), n_out=S + len(src))
     reqs.append(req)
   res = ops.gru_pool_fwd_multi(reqs, tail_stream=evaluation._tail_stream(dev) if tail_stream else None)
   torch.cuda.synchronize()
@@ -122,9 +126,27 @@ def _run_inference(jobs, layers_, data, dev, tail_stream):
   return res
 
 
+def _run_training(jobs, layers_, data, ws, dev):
+  """One layers.run_grouped call of a case with its backward pass, every request on a job stream of
+  its own: per request [out, dx, (dh0,) every parameter gradient]."""
+  from cmhse_amd import layers, ops
+  calls, ins = [], []
+  for j, layer, (lens, x, h0, tok, table) in zip(jobs, layers_, data):
+    layer.zero_grad()
+    xt = torch.from_numpy(x).to(dev).requires_grad_(True)
+    ht = torch.from_numpy(h0).to(dev).requires_grad_(True) if h0 is not None else None
+    calls.append((layer, layers.SeqInput('padded', lens.astype(np.int64), layer.POOL), xt, ht, None))
+    ins.append((xt, ht))
+  st = ops.stream_set(dev)
+  outs = layers.run_grouped(calls, [st[k] for k in range(len(calls))])
+  sum((o * torch.from_numpy(w).to(dev)).sum() for o, w in zip(outs, ws)).backward()
+  torch.cuda.synchronize()
+  return [[o.detach().clone(), xt.grad.clone()] + ([ht.grad.clone()] if ht is not None else []) +
+          [p.grad.clone() for p in layer.parameters()] for o, (xt, ht), layer in zip(outs, ins, layers_)]
+
+
 @pytest.mark.parametrize('case', fwd_shapes.CASES, ids=[_id(c) for c in fwd_shapes.CASES])
 def test_fwd_step_shape_vs_oracle(dev, oracle, tune, case):
-  from cmhse_amd import layers, ops
   name, knobs, train, tail_stream, jobs, _ = case
   layers_, sds, data, rng = _setup(jobs, dev)
   tune(**knobs)
@@ -135,19 +157,7 @@ def test_fwd_step_shape_vs_oracle(dev, oracle, tune, case):
     return [[o.clone()] for o, _ in _run_inference(jobs, layers_, data, dev, tail_stream)]
 
   def run_training():
-    calls, ins = [], []
-    for j, layer, (lens, x, h0, tok, table) in zip(jobs, layers_, data):
-      layer.zero_grad()
-      xt = torch.from_numpy(x).to(dev).requires_grad_(True)
-      ht = torch.from_numpy(h0).to(dev).requires_grad_(True) if h0 is not None else None
-      calls.append((layer, layers.SeqInput('padded', lens.astype(np.int64), layer.POOL), xt, ht, None))
-      ins.append((xt, ht))
-    st = ops.stream_set(dev)
-    outs = layers.run_grouped(calls, [st[k] for k in range(len(calls))])
-    sum((o * torch.from_numpy(w).to(dev)).sum() for o, w in zip(outs, ws)).backward()
-    torch.cuda.synchronize()
-    return [[o.detach().clone(), xt.grad.clone()] + ([ht.grad.clone()] if ht is not None else []) +
-            [p.grad.clone() for p in layer.parameters()] for o, (xt, ht), layer in zip(outs, ins, layers_)]
+    return _run_training(jobs, layers_, data, ws, dev)
 
   run = run_training if train else run_inference
   first, again = run(), run()

@@ -39,6 +39,11 @@ Mutants:
   score_merge_list_not_shifted
                  the tile deal and the panel walk of the scoring kernels (killed by tests/test_gpu_score_shapes.py;
                  which of them an older test catches: profiles/score_shapes_mutation_check.txt)
+  attn_pool_first_round, attn_pool_den_first_trip, attn_pool_first_unit_round, attn_bwd_den_first_trip,
+  attn_bwd_wave_first_step, colsum_two_slabs
+                 the loops that change behaviour only with a sequence's length or past H = 1024 (killed by
+                 tests/test_gpu_long_shapes.py; which of them an older test catches:
+                 profiles/long_shapes_mutation_check.txt)
 """
 import os
 import shutil
@@ -48,6 +53,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 OUT = os.path.join(REPO, 'build', 'mutants')
+RUN_TIMEOUT_S = int(os.environ.get('MUTATION_RUN_TIMEOUT', '1800'))      # one pytest run of `run`
 
 MUTANTS = {
     'attn_eps_fwd': ('gru_attention.hpp', 's_den = d + 0.0001f;', 's_den = d + 0.0f;'),
@@ -175,6 +181,23 @@ MUTANTS = {
     # wave_merge leaves the list entries where they were: harmless into an empty list, wrong into a warm one
     'score_merge_list_not_shifted': ('topk_lists.hpp', 'if (e < K && e + lr[h] < K) lst[e + lr[h]] = lv[h];',
                                      'if (e < K && e + lr[h] < K) lst[e] = lv[h];'),
+    # long sequences (tests/test_gpu_long_shapes.py): value-only edits, no address, grid, barrier or wait changes.
+    # attn_pool_kernel's weighted sum stops after its first round of 256 staged steps: wrong from 257 steps on
+    'attn_pool_first_round': ('gru_attention.hpp', 'for (int t0 = 0; t0 < len; t0 += kThreads) {',
+                              'for (int t0 = 0; t0 < len && t0 < kThreads; t0 += kThreads) {'),
+    # ... its denominator visits each thread's first step only
+    'attn_pool_den_first_trip': ('gru_attention.hpp', 'for (int t = tid; t < len; t += kThreads) {', 'if (int t = tid; t < len) {'),
+    # ... its output loop runs once: the units from 1024 on are never written
+    'attn_pool_first_unit_round': ('gru_attention.hpp', 'for (int ub = 0; ub < H; ub += 4 * kThreads) {',
+                                   'for (int ub = 0; ub < H && ub < 4 * kThreads; ub += 4 * kThreads) {'),
+    # attn_pool_bwd_kernel's denominator visits each thread's first step only: wrong from 1025 steps on
+    'attn_bwd_den_first_trip': ('bwd_pool_kernels.hpp', 'for (int t = tid; t < len; t += NT) part += expf(energy(t));',
+                                'if (int t = tid; t < len) part += expf(energy(t));'),
+    # ... its pass 1 takes only each wave's first step into c = sum_t a_t da_t: wrong from 17 steps on
+    'attn_bwd_wave_first_step': ('bwd_pool_kernels.hpp', '    c_acc += a * d;', '    if (t == wave) c_acc += a * d;'),
+    # d att_w from the first two slabs of 512 packed rows: wrong from 1025 rows on
+    'colsum_two_slabs': ('bwd_pool_kernels.hpp', 'for (int i = 0; i < slabs; ++i) s += part[static_cast<int64_t>(i) * cols + c];',
+                         'for (int i = 0; i < slabs && i < 2; ++i) s += part[static_cast<int64_t>(i) * cols + c];'),
 }
 # mutants that change no result, with the reason: run and reported, but no test can kill them
 EQUIVALENT = {
@@ -185,11 +208,11 @@ EQUIVALENT = {
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
           'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py',
           'tests/test_gpu_loss_shapes.py', 'tests/test_gpu_bf3_shapes.py', 'tests/test_gpu_bwd_side_shapes.py',
-          'tests/test_gpu_score_shapes.py', '-k',
+          'tests/test_gpu_score_shapes.py', 'tests/test_gpu_long_shapes.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
           'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
           'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes or bf3_shape or bwd_side_shape or '
-          'score_shape']
+          'score_shape or long_shape or outlier_paragraph']
 
 
 def build(only=()):
@@ -228,9 +251,17 @@ def run(only=()):
     env = dict(os.environ)
     if name:
       env['CMHSE_HIP_LIB'] = os.path.join(OUT, 'libcmhse_%s.so' % name)
-    res = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-m', 'gpu', '-p', 'no:cacheprovider',
-                          '--tb=line'] + select, cwd=REPO, env=env, stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
+    try:
+      res = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-m', 'gpu', '-p', 'no:cacheprovider',
+                            '--tb=line'] + select, cwd=REPO, env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True, timeout=RUN_TIMEOUT_S)
+    except subprocess.TimeoutExpired:
+      print('=== %s: no end after %d s — nothing more is started on this GPU' % (name or 'product library', RUN_TIMEOUT_S))
+      return 2
+    if res.returncode < 0 or res.returncode in (134, 139):      # the process died (abort, segmentation fault): a finding
+      print('=== %s: the test process died (rc %d) — nothing more is started on this GPU' % (name or 'product library', res.returncode))
+      print(res.stdout[-2000:])
+      return 2
     failed = [l for l in res.stdout.splitlines() if l.startswith('FAILED')]
     errors = [l for l in res.stdout.splitlines() if l.startswith('ERROR')]
     tail = res.stdout.strip().splitlines()[-1] if res.stdout.strip() else ''
