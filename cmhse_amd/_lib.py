@@ -116,6 +116,10 @@ SIGNATURES = {
     'cmhse_sim_topk': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                       c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    'cmhse_sim_topk_exact_workspace': (c_size_t, [c_int32, c_int32, c_int32]),
+    'cmhse_sim_topk_exact': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                            c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
     'cmhse_sim_rank_labelled_workspace': (c_size_t, [c_int32, c_int32]),
     'cmhse_sim_rank_labelled': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                                c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/cmhse_hip.h"
+#include "exact64.hpp"
 #include "gru_ws.hpp"
 #include "nt_core.hpp"
 #include "score_tile.hpp"
@@ -62,21 +63,7 @@ struct SimParams {
   int32_t* resolved;            // [nrows] pairs that went through dot64
 };
 
-// THE float64 score of two fp32 rows: every s64 of cmhse_sim_rank_exact — the diagonal's, an undecided
-// pair's, the squared norms of the tolerance — comes out of this one routine, so two pairs of bit-identical
-// rows have bit-identical scores whichever kernel asked.  One wave, all 64 lanes: lane l runs the chain
-// acc = fma(double(a[k]), double(b[k]), acc) over k = l, l + 64, ... ascending from acc = 0 (the product of
-// two fp32 values is exact in float64: one rounding per term), then the 64 partial sums are added in a
-// butterfly over lane distances 32, 16, 8, 4, 2, 1 (x + y is commutative, so every lane holds the same
-// bits).  Reads are coalesced (256 B per wave and step); the rows are L2-hot in the counting pass.
-__device__ __forceinline__ double dot64(const float* a, const float* b, int D, int lane) {
-  double acc = 0.0;
-  for (int k = lane; k < D; k += 64) acc = fma(static_cast<double>(a[k]), static_cast<double>(b[k]), acc);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-  return acc;
-}
-
+// (dot64, THE float64 score of two fp32 rows, its error bound and the tolerance launch: exact64.hpp)
 constexpr int kExactWords = kSimBM * kSimBN / 32;   // bitmap of a tile's undecided pairs: 2 KB of LDS
 
 // TS = 32 x 32 blocks per wave in each direction: 2 = the 128 x 128 tile; 1 = a 64 x 64 tile for the
@@ -402,44 +389,10 @@ __global__ void label_decode_kernel(const score_key_t* key, float* thr, int32_t*
 }
 
 // ---------------------------------------------------------------------------------------------
-// cmhse_sim_rank_exact: the tolerance, the pre-pass and the last pass around sim_kernel<kSimExact>.
-//
-// The bound.  v(i,j) is the MFMA k-chain: D fused multiply-adds in fp32, one rounding each (unit roundoff
-// u = 2^-24), in an order that does not matter here.  With gamma_n(u) = n u / (1 - n u), the standard
-// bound of such a chain (Higham, Accuracy and Stability of Numerical Algorithms, section 3.1) is
-//   |v(i,j) - a_i . b_j| <= gamma_D(u) sum_k |a_ik b_jk| <= gamma_D(u) |a_i| |b_j|    (Cauchy-Schwarz)
-// as long as no step underflows.  fp32 subnormals are kept here (neither the operands nor the
-// accumulator of the MFMA flush), so a step whose result falls below 2^-126 is off by at most half a
-// subnormal step, 2^-150: D 2^-149 in all, added as an absolute term.  No other assumption is made on
-// small products; the inputs are assumed finite, and D < 2^24.
-// s64(i,j) is dot64: chains of at most ceil(D / 64) fused multiply-adds in float64 (u' = 2^-53; the
-// products are exact) and six more additions: |s64(i,j) - a_i . b_j| <= gamma_{ceil(D/64)+6}(u') |a_i| |b_j|,
-// taken here as (D / 64 + 8) 2^-53 (the denominator 1 - n u' is covered by the slack below).  So
-//   |v(i,j) - s64(i,j)| <= E_i = (gamma_D(u) + (D / 64 + 8) 2^-53) |a_i| max_j |b_j| + D 2^-149
-// for every column j, the diagonal included, and |fl(v(i,j) - v(i,i))| > 2 E_i / (1 - u) decides the sign
-// of s64(i,j) - s64(i,i) (the fp32 subtraction is off by a factor 1 + d, |d| <= u).  What is left is the
-// arithmetic of the tolerance itself: the norms are sqrt(dot64(x, x)), relative error below 2^-45 for
-// D < 2^24; the maximum over j is rounded UP to fp32 before its atomic max; the dozen float64 operations
-// below are off by 2^-53 each; the result, times the tunable rank_exact_tol_scale, is rounded UP to the
-// fp32 the kernel compares with.  All of that, 1 / (1 - u) included, lies far inside the factor 1 + 2^-18.
-// The value stays within 1 + 2^-11 of the textbook 2 D u |a| |b| up to D = 4096: nothing is given away.
+// cmhse_sim_rank_exact: the pre-pass and the last pass around sim_kernel<kSimExact>.  The bound E_i on
+// |v(i,j) - s64(i,j)|, the tolerance 2 E_i (1 + 2^-18) and exact_tol_kernel are exact64.hpp's, shared with
+// cmhse_sim_topk_exact (topk.hip).
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ inline double exact_tolerance(int32_t D, double norm_a, double norm_b_max) {
-  const double du = static_cast<double>(D) * 0x1p-24;
-  if (!(du < 1.0)) return INFINITY;
-  const double gamma = du / (1.0 - du);
-  const double e64 = static_cast<double>(D / 64 + 8) * 0x1p-53;
-  const double e = (gamma + e64) * norm_a * norm_b_max + static_cast<double>(D) * 0x1p-149;
-  return 2.0 * e * (1.0 + 0x1p-18);
-}
-
-// the smallest fp32 that is not below x >= 0
-__device__ __forceinline__ float round_up_f32(double x) {
-  float f = static_cast<float>(x);
-  if (static_cast<double>(f) < x) f = __uint_as_float(__float_as_uint(f) + 1u);   // (f >= 0, finite)
-  return f;
-}
-
 struct ExactPreParams {
   const float* A;            // [N, D]
   const float* B;            // [M, D]
@@ -476,14 +429,6 @@ __global__ __launch_bounds__(kThreads) void exact_pre_kernel(const ExactPreParam
     const double nb = sqrt(dot64(b, b, p.D, lane));
     if (lane == 0) atomicMax(p.norm_b_max, __float_as_uint(round_up_f32(nb)));
   }
-}
-
-__global__ void exact_tol_kernel(const double* norm_a, const unsigned* norm_b_max, float* tol, int32_t D,
-                                 int32_t scale, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double nb = static_cast<double>(__uint_as_float(*norm_b_max));
-  tol[i] = round_up_f32(exact_tolerance(D, norm_a[i], nb) * static_cast<double>(scale));
 }
 
 // rank_hi arrives holding the ties of the resolved pairs

@@ -1031,7 +1031,7 @@ def _from_last_encode(images, captions):
   return None
 
 
-def retrieve(queries, gallery, k=10):
+def retrieve(queries, gallery, k=10, exact=False):
   """Top-k retrieval: for every query row, the k gallery rows with the largest dot product
   (cosine similarity on encode_data's normalised embeddings), best first, smaller gallery index
   first on exact ties (ops.sim_topk: matrix-free, exact fp32).
@@ -1042,11 +1042,19 @@ def retrieve(queries, gallery, k=10):
 
   NumPy in (encode_data's arrays, pinned views included), NumPy out: scores float32 [n, k] and
   index int64 [n, k].  GPU tensors in: device tensors out (float32, int32), on the current
-  stream.  The ranking cache i2t / t2i serve from is neither read nor changed."""
+  stream.  The ranking cache i2t / t2i serve from is neither read nor changed.
+
+  exact=True: the list of the FLOAT64 scores of the same embeddings, certified (ops.sim_topk_exact):
+  its order and its membership at the k-th place depend on neither summation order, tile shape nor
+  machine, where the fp32 list can differ on most rows of a nearly tied gallery.  scores are float64;
+  the rest as above."""
+  if exact not in (False, True):
+    raise ValueError('exact must be False or True, got %r' % (exact,))
+  topk = (lambda q, g: ops.sim_topk_exact(q, g, k)[:2]) if exact else (lambda q, g: ops.sim_topk(q, g, k))
   if isinstance(queries, torch.Tensor) and queries.is_cuda:
-    return ops.sim_topk(queries, _as_device(gallery, queries.device), k)
+    return tuple(topk(queries, _as_device(gallery, queries.device)))
   q = _as_device(queries)
-  scores, index = ops.sim_topk(q, _as_device(gallery, q.device), k)
+  scores, index = topk(q, _as_device(gallery, q.device))
   return scores.cpu().numpy(), index.cpu().numpy().astype(numpy.int64)
 
 
@@ -1200,7 +1208,7 @@ def i2t_t2i_labelled(images, captions, pairs):
           (report_from_ranks(host[2]), host[3], host[2]))
 
 
-def i2t_t2i_exact(images, captions, ties='optimistic'):
+def i2t_t2i_exact(images, captions, ties='optimistic', top1='fp32'):
   """i2t_t2i on the ranks of the FLOAT64 scores of the two matrices, certified (ops.sim_rank_exact):
   independent of summation order, tile shape and machine, where the fp32 ranks of i2t / t2i differ from
   a float64 ranking of the same embeddings on about one row in a few thousand.  Returns
@@ -1209,21 +1217,32 @@ def i2t_t2i_exact(images, captions, ties='optimistic'):
   counted: i2t's rule) and rank_hi for ties='pessimistic' (it is: a collapsed model reports the last
   rank, not the first).  info = {'i2t': d, 't2i': d, 'resolved': total}, each d with 'report_lo',
   'report_hi' (report_from_ranks of the two vectors), 'tied_rows' (the rows with rank_lo < rank_hi) and
-  'resolved' (the pairs that went through float64).  top1 is sim_rank's, not certified.  NumPy arrays or
-  GPU tensors; one device-to-host copy; GPU tensors in: top1 and ranks stay int32 device tensors.  The
-  ranking cache i2t / t2i serve from is neither read nor changed."""
+  'resolved' (the pairs that went through float64).  top1='fp32' (the default): top1 is sim_rank's, not
+  certified; top1='exact': the arg-max of the float64 scores, the smaller index on a float64 tie, from a
+  certified k = 1 retrieval (ops.sim_topk_exact) per direction, whose float64 columns are counted in
+  info['top1_resolved'].  NumPy arrays or GPU tensors; one device-to-host copy; GPU tensors in: top1 and
+  ranks stay int32 device tensors.  The ranking cache i2t / t2i serve from is neither read nor changed."""
   if ties not in ('optimistic', 'pessimistic'):
     raise ValueError("ties must be 'optimistic' or 'pessimistic', got %r" % (ties,))
+  if top1 not in ('fp32', 'exact'):
+    raise ValueError("top1 must be 'fp32' or 'exact', got %r" % (top1,))
   on_device = isinstance(images, torch.Tensor) and images.is_cuda
   v = _as_device(images)
   p = _as_device(captions, v.device)
   out_i = ops.sim_rank_exact(v, p)
   out_t = ops.sim_rank_exact(p, v)
   n, m = out_i[0].numel(), out_t[0].numel()
+  tail = []
+  if top1 == 'exact':
+    _, top_i, res_i = ops.sim_topk_exact(v, p, 1)
+    _, top_t, res_t = ops.sim_topk_exact(p, v, 1)
+    out_i = (out_i[0], out_i[1], top_i.reshape(-1), out_i[3])
+    out_t = (out_t[0], out_t[1], top_t.reshape(-1), out_t[3])
+    tail = [res_i, res_t]        # (per-row counts: summed on the host, where n * M does not overflow)
   # (the two sides may differ in length: one flat vector, cut on the host)
-  flat = torch.cat(list(out_i) + list(out_t)).cpu().numpy()
+  flat = torch.cat(list(out_i) + list(out_t) + tail).cpu().numpy()
   host_i = [x.astype(numpy.float64) for x in numpy.split(flat[:4 * n], 4)] if n else [numpy.zeros(0)] * 4
-  host_t = [x.astype(numpy.float64) for x in numpy.split(flat[4 * n:], 4)] if m else [numpy.zeros(0)] * 4
+  host_t = [x.astype(numpy.float64) for x in numpy.split(flat[4 * n:4 * (n + m)], 4)] if m else [numpy.zeros(0)] * 4
   pick = 0 if ties == 'optimistic' else 1
   info, sides = {}, []
   for name, host, dev in (('i2t', host_i, out_i), ('t2i', host_t, out_t)):
@@ -1232,6 +1251,8 @@ def i2t_t2i_exact(images, captions, ties='optimistic'):
     report = info[name]['report_lo' if pick == 0 else 'report_hi']
     sides.append((report, dev[2], dev[pick]) if on_device else (report, host[2], host[pick]))
   info['resolved'] = info['i2t']['resolved'] + info['t2i']['resolved']
+  if top1 == 'exact':
+    info['top1_resolved'] = int(flat[4 * (n + m):].astype(numpy.int64).sum())
   return sides[0], sides[1], info
 
 

@@ -905,6 +905,36 @@ def sim_topk(queries, gallery, k, row0=0, nrows=None):
   return scores, index
 
 
+def sim_topk_exact(queries, gallery, k, row0=0, nrows=None):
+  """The k best gallery rows of each query row of the stripe [row0, row0+nrows) by the FLOAT64 scores of the
+  fp32 rows, certified (cmhse_sim_topk_exact): device tensors (scores float64 [nrows, k], index int32
+  [nrows, k], resolved int32 [nrows]) on the current stream.  Score descending, smaller index first where
+  two float64 scores are equal (sim_topk's rule); resolved is the number of columns of each row that went
+  through float64 (>= k).  The result depends on neither summation order, tile shape nor machine."""
+  lib = _lib.load()
+  a = _f32c(queries, 'queries')
+  b = _f32c(gallery, 'gallery')
+  N, D = a.shape
+  M = b.shape[0]
+  if b.shape[1] != D:
+    raise ValueError('embedding widths differ')
+  if nrows is None:
+    nrows = N - row0
+  k = int(k)
+  if not 1 <= k <= min(M, _lib.TOPK_MAX):
+    raise ValueError('k must lie in [1, min(gallery rows, %d)], got %d' % (_lib.TOPK_MAX, k))
+  scores = torch.empty(max(nrows, 0), k, dtype=torch.float64, device=a.device)
+  index = torch.empty(max(nrows, 0), k, dtype=torch.int32, device=a.device)
+  resolved = torch.empty(max(nrows, 0), dtype=torch.int32, device=a.device)
+  if nrows != 0:
+    ws_bytes = lib.cmhse_sim_topk_exact_workspace(nrows, M, k)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    rc = lib.cmhse_sim_topk_exact(a.data_ptr(), b.data_ptr(), N, M, D, row0, nrows, k, scores.data_ptr(),
+                                  index.data_ptr(), resolved.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+    _lib.check(rc, 'cmhse_sim_topk_exact')
+  return scores, index, resolved
+
+
 def _label_ints(x, what):
   """`x` as a 1-D int64 array; ValueError unless it holds integers (no bools, no floats)."""
   if isinstance(x, torch.Tensor):

@@ -393,8 +393,8 @@ int cmhse_sim_rank_labelled(const float* A, const float* B, int32_t N, int32_t M
  *   rank_hi[i - row0]  = #{ j != i : s64(i,j) >= s64(i,i) }   the pessimistic rank: above rank_lo only on
  *                        exact float64 ties, which bit-identical gallery rows produce (a collapsed model
  *                        has rank_lo 0 and rank_hi M - 1 everywhere);
- *   top1[i - row0]     = cmhse_sim_rank's, by its fp32 rule, unchanged and NOT certified (certifying the
- *                        arg-max needs the row maximum before the pass);
+ *   top1[i - row0]     = cmhse_sim_rank's, by its fp32 rule, unchanged and NOT certified (the certified
+ *                        arg-max is cmhse_sim_topk_exact with K = 1);
  *   resolved[i - row0] = the pairs of row i that went through float64: a diagnostic, deterministic
  *                        because the classification is.
  * How: the counting pass of cmhse_sim_rank with a per-row tolerance tol_i = 2 E_i, where E_i bounds
@@ -425,6 +425,48 @@ int cmhse_sim_rank_exact(const float* A, const float* B, int32_t N, int32_t M, i
                          int32_t nrows, int32_t* rank_lo /*[nrows]*/, int32_t* rank_hi /*[nrows]*/,
                          int32_t* top1 /*[nrows]*/, int32_t* resolved /*[nrows]*/, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* Certified top-K retrieval: the K best columns of every row by the FLOAT64 scores of the same fp32 rows, at
+ * about twice the cost of cmhse_sim_topk.  A [N,D] queries, B [M,D] gallery, N and M independent (no diagonal
+ * convention), the stripe [row0, row0+nrows).  s64(i,j) is the float64 dot product of cmhse_sim_rank_exact:
+ * the ONE routine with its lane order and its butterfly.  For every row i of the stripe:
+ *   index[i - row0, :]   the first K columns in the order (s64(i,j) descending, then j ascending): the tie
+ *                        rule of cmhse_sim_topk and of top1, applied to the float64 scores.  Two scores that
+ *                        compare equal as doubles tie (-0.0 and +0.0 included);
+ *   scores[i - row0, :]  those s64 values, float64;
+ *   resolved[i - row0]   the columns of row i that went through float64: a diagnostic, >= K, a function of
+ *                        the inputs alone.
+ * How: (1) cmhse_sim_topk into a private region: v_K(i), the K-th fp32 score of the row; (2) one wave per row
+ * of the stripe and of B: |a_i|, max_j |b_j|, and tol_i = 2 E_i (1 + 2^-18) rounded up to fp32, the tolerance
+ * of cmhse_sim_rank_exact (cmhse_sim_rank_exact_tolerance); (3) a second tile pass of the same shape whose
+ * scores are bit-identical to (1)'s: every column with fl(v_K(i) - v(i,j)) <= tol_i is a candidate, gets its
+ * s64 inside the tile that found it, and is merged into the row's list of K (float64 bits, column) pairs in
+ * LDS; (4) one wave per row merges the column panels' lists.  No list of pairs, no capacity, no retry.
+ * Why it is exact: the K columns of the fp32 list have v >= v_K, so s64 >= v_K - E_i, so the K-th largest
+ * s64 of the row is >= v_K - E_i; a member of the float64 top-K has s64 at least that (on a tie at the
+ * boundary too), so v >= v_K - 2 E_i: it is a candidate, and the exact top-K of a superset of the top-K is
+ * the top-K (derived in topk.hip).
+ * Properties: the result does not depend on the tolerance as long as it is valid (the tunable
+ * "rank_exact_tol_scale" multiplies it and only moves `resolved`), nor on tiling, panel count or scheduling;
+ * row stripes concatenate bit for bit; the math mode does not matter.  Inputs are assumed finite.
+ * 1 <= K <= min(M, CMHSE_TOPK_MAX).  Errors, before anything is launched, with the codes and in the order of
+ * cmhse_sim_topk: CMHSE_ERR_ARG for a null A / B, N, M or D <= 0, K outside its range, a stripe outside
+ * [0, N]; nrows == 0: nothing is launched and every other pointer may be NULL; CMHSE_ERR_ARG for a null
+ * scores / index / resolved / workspace; CMHSE_ERR_WORKSPACE for a workspace that is unaligned (256 bytes) or
+ * too small; CMHSE_ERR_UNSUPPORTED for D >= 2^24 (the bound needs D u < 1).
+ * cmhse_sim_topk_exact_workspace(nrows, M, K) (0 for nrows, M <= 0 or K outside [1, CMHSE_TOPK_MAX]):
+ * cmhse_sim_topk_workspace(nrows, M, K) and that call's two outputs (8 bytes x nrows x K), 12 bytes a row of
+ * norm and tolerance (v_K is read from the fp32 list in place), and per column panel 12 bytes x nrows x K of
+ * pairs and 4 x nrows of counts.  The panel count follows cmhse_sim_topk's rule with this pass's LDS size
+ * (64 x K x 12 bytes of lists): fixed by nrows and K, not by M — 30 MB at nrows 4917, M 4917 or 10^6, K 50.
+ * The size is NOT monotone in nrows or K (nor is cmhse_sim_topk_workspace): the panel count is a floor,
+ * 256 x (workgroups per CU) / row tiles, so a larger stripe or K can need less (K = 1, M = 4917: nrows 5440
+ * needs more than nrows 5504).  Size the buffer for the call it serves; a buffer sized for the largest stripe
+ * is not thereby large enough for a smaller one. */
+size_t cmhse_sim_topk_exact_workspace(int32_t nrows, int32_t M, int32_t K);
+int cmhse_sim_topk_exact(const float* A, const float* B, int32_t N, int32_t M, int32_t D, int32_t row0,
+                         int32_t nrows, int32_t K, double* scores /*[nrows,K]*/, int32_t* index /*[nrows,K]*/,
+                         int32_t* resolved /*[nrows]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Group-wise video <-> paragraph scores and ranking from the low-level rows (the score
  * GroupWiseContrastiveLoss trains on, loss.py:26-41; upstream's validate() has its evaluation

@@ -44,6 +44,9 @@ Mutants:
                  the loops that change behaviour only with a sequence's length or past H = 1024 (killed by
                  tests/test_gpu_long_shapes.py; which of them an older test catches:
                  profiles/long_shapes_mutation_check.txt)
+  topk_exact_tol_zero, topk_exact_tol_small, topk_exact_tie_larger_column
+                 the second pass of the certified top-K (killed by tests/test_gpu_topk_exact.py:
+                 profiles/topk_exact_mutation_check.txt)
 """
 import os
 import shutil
@@ -198,6 +201,14 @@ MUTANTS = {
     # d att_w from the first two slabs of 512 packed rows: wrong from 1025 rows on
     'colsum_two_slabs': ('bwd_pool_kernels.hpp', 'for (int i = 0; i < slabs; ++i) s += part[static_cast<int64_t>(i) * cols + c];',
                          'for (int i = 0; i < slabs && i < 2; ++i) s += part[static_cast<int64_t>(i) * cols + c];'),
+    # certified top-K (tests/test_gpu_topk_exact.py): value-only edits as above.
+    # The second pass takes the columns at or above v_K only: the fp32 list's members, re-sorted in float64
+    'topk_exact_tol_zero': ('topk.hip', 'const float tol = s_tol[row];', 'const float tol = 0.f;'),
+    # ... or a tolerance a thousand times too small: about one fp32 step of a unit-norm score
+    'topk_exact_tol_small': ('topk.hip', 'const float tol = s_tol[row];', 'const float tol = s_tol[row] * 1e-3f;'),
+    # equal float64 scores put the LARGER column first
+    'topk_exact_tie_larger_column': ('topk_lists.hpp', 'return xb > yb || (xb == yb && xi < yi);',
+                                     'return xb > yb || (xb == yb && xi > yi);'),
 }
 # mutants that change no result, with the reason: run and reported, but no test can kill them
 EQUIVALENT = {
@@ -208,11 +219,11 @@ EQUIVALENT = {
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
           'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py',
           'tests/test_gpu_loss_shapes.py', 'tests/test_gpu_bf3_shapes.py', 'tests/test_gpu_bwd_side_shapes.py',
-          'tests/test_gpu_score_shapes.py', 'tests/test_gpu_long_shapes.py', '-k',
+          'tests/test_gpu_score_shapes.py', 'tests/test_gpu_long_shapes.py', 'tests/test_gpu_topk_exact.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
           'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
           'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes or bf3_shape or bwd_side_shape or '
-          'score_shape or long_shape or outlier_paragraph']
+          'score_shape or long_shape or outlier_paragraph or topk_exact']
 
 
 def build(only=()):
