@@ -33,8 +33,9 @@ __device__ __forceinline__ void l2norm_row(const float* xr, float* yr, int cols)
   for (int c = threadIdx.x; c < cols; c += kThreads) yr[c] = xr[c] * inv;
 }
 
-// dx = (g - y (y.g)) / max(||x||, eps), y = x / max(||x||, eps); grad(c) is the upstream gradient of
-// column c, evaluated twice per column.
+// dx = (g - y (y.g)) / ||x|| for ||x|| >= eps, y = x / ||x||, and dx = g / eps below it (the clamp
+// passes no gradient to the norm, as torch's clamp_min does not); grad(c) is the upstream gradient
+// of column c, evaluated twice per column.
 template <typename Grad>
 __device__ __forceinline__ void l2norm_bwd_row(const float* xr, float* dxr, int cols, Grad grad) {
   float ss = 0.f, sg = 0.f;
@@ -56,9 +57,11 @@ __device__ __forceinline__ void l2norm_bwd_row(const float* xr, float* dxr, int 
   __syncthreads();
   if (threadIdx.x == 0) {
     const float n2 = p1[0] + p1[1] + p1[2] + p1[3];
-    const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
+    const float nrm = sqrtf(n2);
+    const float inv = 1.0f / fmaxf(nrm, 1e-12f);
     s_inv = inv;
-    s_dot = (p2[0] + p2[1] + p2[2] + p2[3]) * inv * inv;  // (y.g)/||x||
+    // (y.g)/||x||; inside the clamp the denominator is the constant eps: no projection term
+    s_dot = nrm < 1e-12f ? 0.f : (p2[0] + p2[1] + p2[2] + p2[3]) * inv * inv;
   }
   __syncthreads();
   const float inv = s_inv, d = s_dot;

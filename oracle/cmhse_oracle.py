@@ -557,9 +557,12 @@ def pooled_gru_backward(c, dout):
 
 def l2_normalize_backward(x, g, dtype=np.float64):
   x = np.asarray(x, dtype=dtype); g = np.asarray(g, dtype=dtype)
-  nrm = np.maximum(np.sqrt((x * x).sum(axis=1, keepdims=True)), 1e-12)
+  raw = np.sqrt((x * x).sum(axis=1, keepdims=True))
+  nrm = np.maximum(raw, 1e-12)
   y = x / nrm
-  return (g - y * (y * g).sum(axis=1, keepdims=True)) / nrm
+  # inside the clamp the denominator is the constant 1e-12 (clamp_min passes no gradient to the norm)
+  proj = np.where(raw < 1e-12, 0.0, (y * g).sum(axis=1, keepdims=True))
+  return (g - y * proj) / nrm
 
 
 def contrastive_loss_backward(im, s, margin=0.0, max_violation=False, norm=True, dtype=np.float64):

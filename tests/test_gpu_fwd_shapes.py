@@ -63,8 +63,9 @@ def _oracle(oracle, j, x, lens, sd, h0):
 
 
 def _backward(oracle, j, cache, lens, w):
+  """The oracle's gradients for d(out) = w, in the type of the cache."""
   if j['pool'] != 'ALL':
-    return oracle.pooled_gru_backward(cache, w.astype(np.float64))
+    return oracle.pooled_gru_backward(cache, w.astype(cache['hs'].dtype))
   dhs = np.zeros_like(cache['hs'])
   starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
   for i, l in enumerate(lens):
@@ -76,16 +77,34 @@ def _id(case):
   return '%s[%s]' % (case[0], ','.join(sorted(t.replace(' ', '_') for t in case[5])))
 
 
-def _setup(jobs, dev):
+def _apply_regime(regime, layer, inputs, rng):
+  """A value regime of tests/value_regimes.py on one request: (fp32 state dict, x, h0, rng) -> the same,
+  modified, loaded back into the layer.  The lengths and the padding stay as they are."""
+  lens, x, h0, tok, table = inputs
+  assert tok is None, 'a value regime scales the inputs: not for token-fed requests'
+  sd = {n: v.detach().numpy().copy() for n, v in layer.state_dict().items()}
+  sd, x, h0 = regime(sd, x.copy(), None if h0 is None else h0.copy(), rng)
+  layer.load_state_dict({n: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for n, v in sd.items()})
+  x = np.ascontiguousarray(x, dtype=np.float32)
+  for i, l in enumerate(lens):
+    assert not x[i, l:].any()
+  return layer, (lens, x, None if h0 is None else np.ascontiguousarray(h0, dtype=np.float32), tok, table)
+
+
+def _setup(jobs, dev, regime=None):
   """The layers of a case's requests (on `dev`), their float64 state dicts, the inputs (_inputs) and
-  the case's random stream."""
+  the case's random stream.  `regime` (tests/value_regimes.py) modifies every request's numbers after
+  they are drawn, from a random stream of its own: the baseline numbers of a case do not depend on it."""
   rng = np.random.RandomState(sum(j['counts'][0] + 3 * j['H'] for j in jobs))
   layers_, sds, data = [], [], []
   for k, j in enumerate(jobs):
     layer = _layer(j['pool'], j['I'], j['H'], seed=17 * k + j['H'])
+    inputs = _inputs(j, rng, dev)
+    if regime is not None:
+      layer, inputs = _apply_regime(regime, layer, inputs, np.random.RandomState(977 + k))
     sds.append({'rnn.' + n: v.detach().numpy().astype(np.float64) for n, v in layer.state_dict().items()})
     layers_.append(layer.to(dev))
-    data.append(_inputs(j, rng, dev))
+    data.append(inputs)
   return layers_, sds, data, rng
 
 
@@ -126,9 +145,10 @@ def _run_inference(jobs, layers_, data, dev, tail_stream):
   return res
 
 
-def _run_training(jobs, layers_, data, ws, dev):
+def _run_training(jobs, layers_, data, ws, dev, after_forward=None):
   """One layers.run_grouped call of a case with its backward pass, every request on a job stream of
-  its own: per request [out, dx, (dh0,) every parameter gradient]."""
+  its own: per request [out, dx, (dh0,) every parameter gradient].  `after_forward()` runs between the
+  two passes, the forward finished (a test reads what the forward saved before the backward runs)."""
   from cmhse_amd import layers, ops
   calls, ins = [], []
   for j, layer, (lens, x, h0, tok, table) in zip(jobs, layers_, data):
@@ -139,6 +159,9 @@ def _run_training(jobs, layers_, data, ws, dev):
     ins.append((xt, ht))
   st = ops.stream_set(dev)
   outs = layers.run_grouped(calls, [st[k] for k in range(len(calls))])
+  if after_forward is not None:
+    torch.cuda.synchronize()
+    after_forward()
   sum((o * torch.from_numpy(w).to(dev)).sum() for o, w in zip(outs, ws)).backward()
   torch.cuda.synchronize()
   return [[o.detach().clone(), xt.grad.clone()] + ([ht.grad.clone()] if ht is not None else []) +

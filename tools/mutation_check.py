@@ -44,6 +44,10 @@ Mutants:
                  the loops that change behaviour only with a sequence's length or past H = 1024 (killed by
                  tests/test_gpu_long_shapes.py; which of them an older test catches:
                  profiles/long_shapes_mutation_check.txt)
+  tanh_cancels_near_zero, tanh_ratio_form, sigmoid_clamps_argument, mid_max_tie_later_step, fwd_tail_max_tie_later_step,
+  attn_den_clamps_energy, attn_bwd_unit_sum, l2norm_bwd_projects_inside_clamp
+                 value-only edits that are wrong only at extreme numbers (killed by tests/test_gpu_value_regimes.py;
+                 none of them by an older test: profiles/value_regimes_mutation_check.txt)
   topk_exact_tol_zero, topk_exact_tol_small, topk_exact_tie_larger_column
                  the second pass of the certified top-K (killed by tests/test_gpu_topk_exact.py:
                  profiles/topk_exact_mutation_check.txt)
@@ -59,6 +63,24 @@ OUT = os.path.join(REPO, 'build', 'mutants')
 RUN_TIMEOUT_S = int(os.environ.get('MUTATION_RUN_TIMEOUT', '1800'))      # one pytest run of `run`
 
 MUTANTS = {
+    # value regimes (tests/value_regimes.py): value-only edits that are wrong only at extreme numbers
+    # ... the form before the polynomial branch: relative error ~1e-7 / |x| near 0
+    'tanh_cancels_near_zero': ('gru_step_tile.hpp', 'return fabsf(x) < kTanhSmall ? poly : big;', 'return big;'),
+    # ... (e - 1) / (e + 1): inf * 0 once exp(2x) overflows
+    'tanh_ratio_form': ('gru_step_tile.hpp', 'const float big = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f);',
+                        'const float big = (__expf(2.0f * x) - 1.0f) * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f);'),
+    # ... a sigmoid that clamps its argument: 1 - 1.1e-7 where the reference gives exactly 1
+    'sigmoid_clamps_argument': ('gru_step_tile.hpp', 'return __builtin_amdgcn_rcpf(1.0f + __expf(-x));',
+                                'return __builtin_amdgcn_rcpf(1.0f + __expf(-fminf(fmaxf(x, -16.0f), 16.0f)));'),
+    # ... the running maximum's tie rule (strict '>': the first maximum wins) where the forward saves the arg-max
+    'mid_max_tie_later_step': ('gru_small_batch.hpp', 'if (p.t == 0 || hn > *op) {', 'if (p.t == 0 || hn >= *op) {'),
+    'fwd_tail_max_tie_later_step': ('gru_small_batch.hpp', 'if (hn > *op) {      // (t >= 1 here', 'if (hn >= *op) {      // (t >= 1 here'),
+    # ... a softmax denominator that clamps its energies / a Jacobian that takes the weights to sum to 1
+    'attn_den_clamps_energy': ('gru_attention.hpp', 'part += expf(e);', 'part += expf(fminf(e, 30.0f));'),
+    'attn_bwd_unit_sum': ('bwd_pool_kernels.hpp', 'if (lane == 0) q.de[row] = a * (q.de[row] - c);',
+                          'if (lane == 0) q.de[row] = a * (q.de[row] - c / (1.0f - 0.0001f / den));'),
+    # ... the projection term inside the 1e-12 clamp of F.normalize's backward
+    'l2norm_bwd_projects_inside_clamp': ('norm_rows.hpp', 's_dot = nrm < 1e-12f ? 0.f : (', 's_dot = false ? 0.f : ('),
     'attn_eps_fwd': ('gru_attention.hpp', 's_den = d + 0.0001f;', 's_den = d + 0.0f;'),
     'attn_eps_bwd': ('bwd_pool_kernels.hpp', 's_den = d + 0.0001f;', 's_den = d + 0.0f;'),
     # loss.py:114-115: `norm` divides by n * m, not by n
@@ -219,11 +241,12 @@ EQUIVALENT = {
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
           'tests/test_gpu_bptt_shapes.py', 'tests/test_gpu_fwd_shapes.py', 'tests/test_gpu_chain.py',
           'tests/test_gpu_loss_shapes.py', 'tests/test_gpu_bf3_shapes.py', 'tests/test_gpu_bwd_side_shapes.py',
-          'tests/test_gpu_score_shapes.py', 'tests/test_gpu_long_shapes.py', 'tests/test_gpu_topk_exact.py', '-k',
+          'tests/test_gpu_score_shapes.py', 'tests/test_gpu_long_shapes.py', 'tests/test_gpu_topk_exact.py',
+          'tests/test_gpu_value_regimes.py', '-k',
           'epsilon or test_layers_vs_golden or test_layer_backward_vs_golden or test_model_vs_golden or norm or '
           'test_gru_pool_vs_oracle or tie or zero or l2norm or test_contrastive_vs_oracle or bptt_step_shape or '
           'mixed_step_shapes or bptt_tail or fwd_step_shape or forward_tail or loss_shapes or bf3_shape or bwd_side_shape or '
-          'score_shape or long_shape or outlier_paragraph or topk_exact']
+          'score_shape or long_shape or outlier_paragraph or topk_exact or value_regime or at_the_clamp or stays_in_its_row']
 
 
 def build(only=()):
