@@ -130,6 +130,11 @@ SIGNATURES = {
     'cmhse_sim_rank_exact': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_size_t, c_void_p]),
+    'cmhse_sim_rank_labelled_exact_workspace': (c_size_t, [c_int32, c_int32]),
+    'cmhse_sim_rank_labelled_exact': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_size_t, c_void_p]),
     'cmhse_group_plan': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32]),
     'cmhse_group_scores': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                           c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),

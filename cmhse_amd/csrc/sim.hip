@@ -12,6 +12,9 @@
 //   cmhse_sim_rank_exact  the ranking of the FLOAT64 scores of the same rows, as an interval [optimistic,
 //                         pessimistic]: the counting pass decides every comparison that the fp32 scores
 //                         provably decide and recomputes the others in float64 inside the tile.
+//   cmhse_sim_rank_labelled_exact  the certified interval for any set of positives per query, any gallery
+//                         size: a float64 threshold pass over the (query, positive) pairs, then the
+//                         certified counting pass against the rounded threshold, no column excluded.
 //   cmhse_cosine_sim      loss.cosine_sim       (/root/reference/loss.py:12-13): the stored-score GEMM,
 //                         which the training losses of loss.hip launch through sim_store.hpp
 //
@@ -41,7 +44,10 @@ constexpr int kSimSmallMax = 512;   // stored-score matrices up to this size use
 // per-row threshold (the best positive's score) instead of the diagonal and no column is excluded.
 // kSimExact: the counting pass of cmhse_sim_rank_exact — kSimRank's with a per-row tolerance: two compares
 // per element, and the pairs neither decides go through dot64 (below) before the workgroup leaves.
-enum { kSimDiag = 0, kSimRank = 1, kSimStore = 2, kSimLabel = 3, kSimExact = 4 };
+// kSimLabelExact: the counting pass of cmhse_sim_rank_labelled_exact — kSimExact's, except that p.diag holds
+// thr32(i) = float(thr64(i)) and p.s64_diag holds thr64(i), the float64 score of the query's best positive,
+// and no column is excluded (kSimLabel's relation to kSimRank).
+enum { kSimDiag = 0, kSimRank = 1, kSimStore = 2, kSimLabel = 3, kSimExact = 4, kSimLabelExact = 5 };
 
 struct SimParams {
   const float* A;  // [N, D]
@@ -56,10 +62,10 @@ struct SimParams {
   // scores of block b at scores + b * blk_stride, leading dimension = the block's size
   const int32_t* blk_off;
   int64_t blk_stride;
-  // kSimExact only (behind everything the other modes read)
+  // kSimExact / kSimLabelExact only (behind everything the other modes read)
   const float* tol;             // [nrows] the certified half-width of "undecided" around diag[i]
-  const double* s64_diag;       // [nrows] dot64 of row i with its diagonal column
-  int32_t* ties;                // [nrows] resolved pairs whose float64 score EQUALS the diagonal's
+  const double* s64_diag;       // [nrows] dot64 of row i with its diagonal column (kSimLabelExact: thr64(i))
+  int32_t* ties;                // [nrows] resolved pairs whose float64 score EQUALS the diagonal's (the threshold)
   int32_t* resolved;            // [nrows] pairs that went through dot64
 };
 
@@ -101,8 +107,9 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
         (static_cast<uint64_t>(__builtin_amdgcn_s_getreg((31 << 11) | 20)) << 32);
   }
 #endif
-  constexpr bool COUNT = MODE == kSimRank || MODE == kSimLabel || MODE == kSimExact;   // the counting passes
-  static_assert(MODE != kSimExact || TS == 2, "the bitmap is laid out for the 128 x 128 tile");
+  constexpr bool EXACT = MODE == kSimExact || MODE == kSimLabelExact;                  // the certified ones
+  constexpr bool COUNT = MODE == kSimRank || MODE == kSimLabel || EXACT;               // the counting passes
+  static_assert(!EXACT || TS == 2, "the bitmap is laid out for the 128 x 128 tile");
   SimParams p = p_;
   if (p.blk_off != nullptr) {
     const int off = p.blk_off[blockIdx.y];
@@ -154,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
   float my_diag = 0.f;
   if (COUNT && tid < BM) my_diag = (i0 + tid < p.nrows) ? p.diag[i0 + tid] : 0.f;
   float my_tol = 0.f;
-  if (MODE == kSimExact && tid < BM) my_tol = (i0 + tid < p.nrows) ? p.tol[i0 + tid] : 0.f;
+  if (EXACT && tid < BM) my_tol = (i0 + tid < p.nrows) ? p.tol[i0 + tid] : 0.f;
   SIM_MARK(1);
   SIM_CLOCK(5);
   nt_phase<BM, BN, TS, TS, TS, TS - 1, VEC>(smem, ar, av, br, bv, p.D, wm * 32 * TS, b_row0, acc);
@@ -166,14 +173,14 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
     // nothing: 404 / 407 us per launch)
     __syncthreads();                 // every wave has read its last fragments
     if (tid < BM) smem[tid] = my_diag;
-    if (MODE == kSimExact) {
+    if (EXACT) {
       if (tid < BM) smem[BM + tid] = my_tol;
       if (tid == 0) smem[2 * BM + kExactWords] = 0.f;    // "some pair of this tile is undecided"
     }
     __syncthreads();
   }
-  // kSimExact, behind the diagonals and tolerances: word 4 row + c holds the undecided pairs of tile row
-  // `row` and tile columns [32 c, 32 c + 32), bit = column; every word is written below, by one half-wave
+  // kSimExact / kSimLabelExact, behind the diagonals and tolerances: word 4 row + c holds the undecided pairs of
+  // tile row `row` and tile columns [32 c, 32 c + 32), bit = column; every word is written below, by one half-wave
   unsigned* const s_amb = reinterpret_cast<unsigned*>(smem + 2 * BM);
 
 #pragma unroll
@@ -205,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
         // (profiles/r04_sim_kernel_trace.txt).  Same count, same key (ordered bits of the score,
         // then the smaller column), same atomics.
         const float dii = smem[li - i0];          // (0 for rows past the stripe: never counted)
-        const float tol = (MODE == kSimExact) ? smem[BM + li - i0] : 0.f;
+        const float tol = EXACT ? smem[BM + li - i0] : 0.f;
         const bool hi = lane >= 32;
         int cnt = 0;
         unsigned ob[TS];
@@ -216,11 +223,11 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
           const float v = acc[ms][ns][r];
           const bool valid = rok && j < p.M;
           unsigned long long gt;
-          if (MODE == kSimExact) {
+          if (EXACT) {
             // surely above: fl(v - dii) > tol; surely below: fl(dii - v) = -fl(v - dii) > tol; else undecided
             // (tol >= 0, possibly +inf: everything undecided; inputs finite, so the difference is no NaN)
             const float diff = v - dii;
-            const bool mine = valid && j != gi;
+            const bool mine = valid && (MODE == kSimLabelExact || j != gi);
             gt = __ballot(mine && diff > tol);
             const unsigned long long amb = __ballot(mine && fabsf(diff) <= tol);
             if ((lane & 31) == 0) {
@@ -254,12 +261,12 @@ __global__ __launch_bounds__(kThreads) void sim_kernel(const SimParams p_) {
       }
     }
   }
-  if (MODE == kSimExact) {
+  if (EXACT) {
     // The resolve step.  The barrier and the test are workgroup-uniform (every thread of a workgroup that
     // gets here reads the same LDS word), the loops are bounded by the 512 bitmap words and their 32 bits,
     // and nothing waits on another workgroup.  Wave w takes the words w, w + 4, ...: the 32 columns of one
     // tile row each; every set bit is one dot64 of that row with the bit's column, compared with the row's
-    // dot64 diagonal.  Integer atomics: the sums do not depend on who adds first.
+    // dot64 diagonal (kSimLabelExact: its float64 threshold).  Integer atomics: the sums do not depend on who adds first.
     __syncthreads();
     if (smem[2 * BM + kExactWords] != 0.f) {
       for (int w = wave; w < kExactWords; w += kThreads / 64) {
@@ -440,6 +447,146 @@ __global__ void exact_finalize_kernel(const score_key_t* key, const int32_t* ran
   rank_hi[i] += rank_lo[i];
 }
 
+// ---------------------------------------------------------------------------------------------
+// cmhse_sim_rank_labelled_exact: the launches around sim_kernel<kSimLabelExact>.
+//
+// thr64(i) = max over p in P_i of s64(i,p) is itself a float64 score (the best positive under fp32 is not always
+// the best positive under float64, so the fp32 threshold pass cannot serve), and the counting pass compares the
+// fp32 MFMA scores v(i,j) with its rounding thr32(i) = float(thr64(i)).  Why tol_i = 2 E_i (1 + 2^-18)
+// (exact64.hpp) stays valid unchanged:
+//   |v(i,j) - s64(i,j)| <= E_i                                               as for cmhse_sim_rank_exact;
+//   |thr32 - thr64| <= u |thr64| <= u (1 + (D / 64 + 8) 2^-53) |a_i| max_j |b_j|   round to nearest, normal range
+//                   <= gamma_D(u) |a_i| max_j |b_j| <= E_i      gamma_D >= gamma_1 = u / (1 - u) = u (1 + 2^-24 + ...),
+//                                                               which covers the factor 1 + (D / 64 + 8) 2^-53 for
+//                                                               D < 2^24;
+//   where thr64 falls into the fp32 subnormal range the rounding is off by at most 2^-150 instead, and
+//   u |thr64| + 2^-150 <= gamma_D(u) |a_i| max_j |b_j| + D 2^-149 <= E_i covers both cases at once.
+// So |(v - thr32) - (s64(i,j) - thr64)| <= 2 E_i, the fp32 subtraction adds a factor 1 + d, |d| <= u, exactly as
+// in the diagonal call (where the second term is |v(i,i) - s64(i,i)| <= E_i), and fl(v - thr32) > tol_i proves
+// s64(i,j) > thr64(i); the reverse likewise.  No gap found: the tolerance is not widened.  thr32 is finite
+// whenever the fp32 scores are (|thr64| <= |a_i| max |b_j| (1 + tiny)); inputs whose fp32 scores overflow are
+// outside the contract here as in the diagonal call.
+// A column whose s64 EQUALS thr64 is never decided by the two compares (either would prove a strict
+// inequality), so every tie — the best positive's own column, other positives at the threshold, tied negatives
+// — reaches the resolve step and is counted in `ties`; the threshold pass counts the list entries at the
+// threshold (lists are strictly ascending: distinct columns), and rank_hi = rank_lo + ties - that count.
+// ---------------------------------------------------------------------------------------------
+struct LabelExactPreParams {
+  const float* A;            // [N, D]
+  const float* B;            // [M, D]
+  int32_t M, D, row0, nrows;
+  double* norm_a;            // [nrows]
+  unsigned* norm_b_max;      // as ExactPreParams'
+  int32_t* rank_lo;          // [nrows] the call's counters, zeroed here
+  int32_t* ties;
+  int32_t* resolved;
+  score_key_t* top1key;
+};
+
+// exact_pre_kernel without the diagonal (there is none: M may be smaller than N)
+__global__ __launch_bounds__(kThreads) void label_exact_pre_kernel(const LabelExactPreParams p) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6);
+  if (r < p.nrows) {
+    const float* a = p.A + (static_cast<int64_t>(p.row0) + r) * p.D;
+    const double na = sqrt(dot64(a, a, p.D, lane));
+    if (lane == 0) {
+      p.norm_a[r] = na;
+      p.rank_lo[r] = 0;
+      p.ties[r] = 0;
+      p.resolved[r] = 0;
+      p.top1key[r] = 0ull;
+    }
+  } else if (r < static_cast<int64_t>(p.nrows) + p.M) {
+    const float* b = p.B + (r - p.nrows) * p.D;
+    const double nb = sqrt(dot64(b, b, p.D, lane));
+    if (lane == 0) atomicMax(p.norm_b_max, __float_as_uint(round_up_f32(nb)));
+  }
+}
+
+struct PairExactParams {
+  const float* A;            // [N, D]
+  const float* B;            // [M, D]
+  int32_t M, D, row0, nrows, n_pairs;
+  const int32_t* pos_off;    // [nrows + 1] device copy
+  const int32_t* pos_idx;    // [n_pairs]   device copy
+  double* pair64;            // [n_pairs] s64 of every pair, CSR order
+  double* thr64;             // [nrows]
+  float* thr32;              // [nrows] float(thr64): what the counting pass compares with
+  int32_t* at_thr;           // [nrows] list entries whose s64 equals thr64
+  int32_t* best_pos;         // [nrows]
+  double* best_score;        // [nrows] or null
+};
+
+// The float64 threshold pass, first half: one wave per pair of the CSR, pair64[g] = s64(query of g, pos_idx[g]).
+// The query of a pair and the clamp of its column are pair_threshold_kernel's (wave-uniform here).
+__global__ __launch_bounds__(kThreads) void pair_exact_kernel(const PairExactParams p) {
+  const int lane = threadIdx.x & 63;
+  const int64_t g64 = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6);
+  if (g64 >= p.n_pairs) return;
+  const int g = static_cast<int>(g64);
+  // the last q with pos_off[q] <= g, inside [g - (n_pairs - nrows), min(g, nrows - 1)]: every index read lies
+  // in [0, nrows), whatever the arrays hold
+  int lo = g - (p.n_pairs - p.nrows), hi = (g < p.nrows - 1) ? g : p.nrows - 1;
+  lo = lo < 0 ? 0 : lo;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (p.pos_off[mid] <= g) lo = mid; else hi = mid - 1;
+  }
+  int c = p.pos_idx[g];
+  c = c < 0 ? 0 : (c < p.M ? c : p.M - 1);   // (validated on the host copy; keeps a differing device copy inside B)
+  const double s = dot64(p.A + static_cast<int64_t>(p.row0 + lo) * p.D, p.B + static_cast<int64_t>(c) * p.D, p.D, lane);
+  if (lane == 0) p.pair64[g] = s;
+}
+
+// Second half: one wave per query reduces its list to (thr64, the smallest column at thr64, the entries at
+// thr64).  Lane l folds the entries l, l + 64, ... of the list, the 64 partial results are combined in a
+// butterfly; (max, then min of the column, then sum of the counts) is associative and commutative in exact
+// arithmetic — no rounding anywhere — so the result does not depend on the order, and nothing here is atomic.
+__global__ __launch_bounds__(kThreads) void label_exact_reduce_kernel(const PairExactParams p) {
+  const int lane = threadIdx.x & 63;
+  const int64_t q64 = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6);
+  if (q64 >= p.nrows) return;
+  const int q = static_cast<int>(q64);
+  // (validated on the host copy; the clamps keep a differing device copy inside pair64 and pos_idx)
+  int beg = p.pos_off[q], end = p.pos_off[q + 1];
+  beg = beg < 0 ? 0 : (beg < p.n_pairs ? beg : p.n_pairs);
+  end = end < beg ? beg : (end < p.n_pairs ? end : p.n_pairs);
+  double best = -INFINITY;      // (every s64 is finite: products of fp32 values, D < 2^24 of them)
+  int col = 0x7fffffff, cnt = 0;
+  for (int e = beg + lane; e < end; e += 64) {
+    const double s = p.pair64[e];
+    int c = p.pos_idx[e];
+    c = c < 0 ? 0 : (c < p.M ? c : p.M - 1);
+    if (s > best) best = s, col = c, cnt = 1;
+    else if (s == best) col = c < col ? c : col, ++cnt;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const double ob = __shfl_xor(best, d, 64);
+    const int oc = __shfl_xor(col, d, 64), on = __shfl_xor(cnt, d, 64);
+    if (ob > best) best = ob, col = oc, cnt = on;
+    else if (ob == best) col = oc < col ? oc : col, cnt += on;
+  }
+  if (lane == 0) {
+    if (cnt == 0) best = 0.0, col = 0;    // (an empty list: only a device copy that differs from the host's)
+    p.thr64[q] = best;
+    p.thr32[q] = static_cast<float>(best);
+    p.at_thr[q] = cnt;
+    p.best_pos[q] = col;
+    if (p.best_score) p.best_score[q] = best;
+  }
+}
+
+// rank_hi arrives holding the ties of the resolved pairs, the list entries at the threshold among them
+__global__ void label_exact_finalize_kernel(const score_key_t* key, const int32_t* rank_lo, int32_t* rank_hi,
+                                            const int32_t* at_thr, int32_t* top1, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  top1[i] = key_index(key[i]);
+  rank_hi[i] += rank_lo[i] - at_thr[i];
+}
+
 // The stored-score GEMM (sim_store.hpp): the one place that chooses its tile size.
 int launch_sim_store(const float* A, const float* B, int n, int m, int D, float* scores,
                      hipStream_t stream, const int32_t* blk_off, int n_blocks, int64_t blk_stride) {
@@ -556,6 +703,39 @@ ExactWs exact_ws(int32_t nrows) {
   L.total = off;
   return L;
 }
+
+// The SimParams and the tile deal of a certified counting pass (kSimExact, kSimLabelExact): one setup for the
+// two calls.  thr32 / thr64 are the fp32 and float64 values every row is compared with (the diagonal score
+// or the best positive's); rank_hi collects the ties until the call's last launch.
+int exact_count_params(SimParams* p_, int64_t* blocks, const float* A, const float* B, int32_t N, int32_t M,
+                       int32_t D, int32_t row0, int32_t nrows, float* thr32, const double* thr64,
+                       score_key_t* top1key, const float* tol, int32_t* rank_lo, int32_t* rank_hi,
+                       int32_t* resolved) {
+  SimParams& p = *p_;
+  p.A = A;
+  p.B = B;
+  p.N = N;
+  p.M = M;
+  p.D = D;
+  p.row0 = row0;
+  p.nrows = nrows;
+  p.n_tiles = (M + kSimBN - 1) / kSimBN;
+  p.diag = thr32;
+  p.top1key = top1key;
+  p.rank = rank_lo;
+  p.scores = nullptr;
+  p.blk_off = nullptr;
+  p.blk_stride = 0;
+  p.tol = tol;
+  p.s64_diag = thr64;
+  p.ties = rank_hi;
+  p.resolved = resolved;
+  const int m_tiles = (nrows + kSimBM - 1) / kSimBM;
+  const XcdDeal deal = xcd_deal(m_tiles, p.n_tiles);
+  p.group = deal.group;
+  *blocks = deal.blocks;
+  return deal.blocks > 0x7fffffffLL ? CMHSE_ERR_UNSUPPORTED : CMHSE_OK;
+}
 }  // namespace
 
 extern "C" size_t cmhse_sim_rank_exact_workspace(int32_t nrows) {
@@ -585,28 +765,13 @@ extern "C" int cmhse_sim_rank_exact(const float* A, const float* B, int32_t N, i
   const ExactWs L = exact_ws(nrows);
   char* const ws = static_cast<char*>(workspace);
   SimParams p;
-  p.A = A;
-  p.B = B;
-  p.N = N;
-  p.M = M;
-  p.D = D;
-  p.row0 = row0;
-  p.nrows = nrows;
-  p.n_tiles = (M + kSimBN - 1) / kSimBN;
-  p.diag = reinterpret_cast<float*>(ws + L.diag);
-  p.top1key = reinterpret_cast<score_key_t*>(ws + L.top1key);
-  p.rank = rank_lo;
-  p.scores = nullptr;
-  p.blk_off = nullptr;
-  p.blk_stride = 0;
-  p.tol = reinterpret_cast<float*>(ws + L.tol);
-  p.s64_diag = reinterpret_cast<double*>(ws + L.s64_diag);
-  p.ties = rank_hi;
-  p.resolved = resolved;
+  int64_t blocks;
+  int rc = exact_count_params(&p, &blocks, A, B, N, M, D, row0, nrows, reinterpret_cast<float*>(ws + L.diag),
+                              reinterpret_cast<double*>(ws + L.s64_diag),
+                              reinterpret_cast<score_key_t*>(ws + L.top1key),
+                              reinterpret_cast<float*>(ws + L.tol), rank_lo, rank_hi, resolved);
+  if (rc != CMHSE_OK) return rc;
   const int m_tiles = (nrows + kSimBM - 1) / kSimBM;
-  const XcdDeal deal = xcd_deal(m_tiles, p.n_tiles);
-  p.group = deal.group;
-  if (deal.blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
   ExactPreParams q;
   q.A = A;
   q.B = B;
@@ -629,10 +794,10 @@ extern "C" int cmhse_sim_rank_exact(const float* A, const float* B, int32_t N, i
   hipLaunchKernelGGL(exact_tol_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream, q.norm_a,
                      q.norm_b_max, reinterpret_cast<float*>(ws + L.tol), D, scale, nrows);
   const size_t smem = TileSmem<kSimBM, kSimBN>::kBytes;
-  int rc = launch_tiles(sim_kernel<kSimDiag, true>, sim_kernel<kSimDiag, false>, D, dim3(m_tiles), smem, stream, p);
+  rc = launch_tiles(sim_kernel<kSimDiag, true>, sim_kernel<kSimDiag, false>, D, dim3(m_tiles), smem, stream, p);
   if (rc != CMHSE_OK) return rc;
   rc = launch_tiles(sim_kernel<kSimExact, true>, sim_kernel<kSimExact, false>, D,
-                    dim3(static_cast<unsigned>(deal.blocks)), smem, stream, p);
+                    dim3(static_cast<unsigned>(blocks)), smem, stream, p);
   if (rc != CMHSE_OK) return rc;
   hipLaunchKernelGGL(exact_finalize_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream, p.top1key,
                      rank_lo, rank_hi, top1, nrows);
@@ -711,6 +876,117 @@ extern "C" int cmhse_sim_rank_labelled(const float* A, const float* B, int32_t N
   if (rc != CMHSE_OK) return rc;
   hipLaunchKernelGGL(top1_finalize_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream,
                      p.top1key, top1, nrows);
+  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
+}
+
+namespace {
+struct LabelExactWs {
+  size_t thr32, top1key, thr64, norm_a, tol, norm_b_max, at_thr, pair64, total;
+};
+LabelExactWs label_exact_ws(int32_t nrows, int32_t n_pairs) {
+  const size_t n = static_cast<size_t>(nrows);
+  LabelExactWs L;
+  size_t off = 0;
+  L.thr32 = off, off += align256(n * sizeof(float));
+  L.top1key = off, off += align256(n * sizeof(score_key_t));
+  L.thr64 = off, off += align256(n * sizeof(double));
+  L.norm_a = off, off += align256(n * sizeof(double));
+  L.tol = off, off += align256(n * sizeof(float));
+  L.norm_b_max = off, off += 256;
+  L.at_thr = off, off += align256(n * sizeof(int32_t));
+  L.pair64 = off, off += align256(static_cast<size_t>(n_pairs) * sizeof(double));
+  L.total = off;
+  return L;
+}
+}  // namespace
+
+extern "C" size_t cmhse_sim_rank_labelled_exact_workspace(int32_t nrows, int32_t n_pairs) {
+  if (nrows <= 0 || n_pairs < nrows) return 0;   // (n_pairs: every query has a positive)
+  return label_exact_ws(nrows, n_pairs).total;
+}
+
+extern "C" int cmhse_sim_rank_labelled_exact(const float* A, const float* B, int32_t N, int32_t M, int32_t D,
+                                             int32_t row0, int32_t nrows, const int32_t* pos_off_host,
+                                             const int32_t* pos_idx_host, const int32_t* pos_off,
+                                             const int32_t* pos_idx, int32_t n_pairs, int32_t* rank_lo,
+                                             int32_t* rank_hi, int32_t* top1, int32_t* best_pos,
+                                             double* best_score, int32_t* resolved, void* workspace,
+                                             size_t workspace_bytes, void* stream_) {
+  if (!A || !B) return CMHSE_ERR_ARG;
+  if (N <= 0 || M <= 0 || D <= 0) return CMHSE_ERR_ARG;
+  if (row0 < 0 || nrows < 0 || static_cast<int64_t>(row0) + nrows > N) return CMHSE_ERR_ARG;
+  if (nrows == 0) return n_pairs == 0 ? CMHSE_OK : CMHSE_ERR_ARG;
+  if (!pos_off_host || !pos_idx_host || !pos_off || !pos_idx || n_pairs < nrows) return CMHSE_ERR_ARG;
+  // the labels, in full, on the host copy: nothing is launched on a list that fails
+  if (pos_off_host[0] != 0 || pos_off_host[nrows] != n_pairs) return CMHSE_ERR_ARG;
+  for (int32_t i = 0; i < nrows; ++i)
+    if (pos_off_host[i + 1] <= pos_off_host[i]) return CMHSE_ERR_ARG;
+  for (int32_t e = 0; e < n_pairs; ++e)
+    if (pos_idx_host[e] < 0 || pos_idx_host[e] >= M) return CMHSE_ERR_ARG;
+  // (the offsets increase from 0 to n_pairs: every e below lies inside pos_idx_host)
+  for (int32_t i = 0; i < nrows; ++i)            // strictly ascending: rank_hi needs DISTINCT positives
+    for (int32_t e = pos_off_host[i] + 1; e < pos_off_host[i + 1]; ++e)
+      if (pos_idx_host[e] <= pos_idx_host[e - 1]) return CMHSE_ERR_ARG;
+  if (!rank_lo || !rank_hi || !top1 || !best_pos || !resolved || !workspace) return CMHSE_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
+      workspace_bytes < cmhse_sim_rank_labelled_exact_workspace(nrows, n_pairs))
+    return CMHSE_ERR_WORKSPACE;
+  if (D >= (1 << 24)) return CMHSE_ERR_UNSUPPORTED;   // (the bound needs D u < 1)
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const LabelExactWs L = label_exact_ws(nrows, n_pairs);
+  char* const ws = static_cast<char*>(workspace);
+  SimParams p;
+  int64_t blocks;
+  int rc = exact_count_params(&p, &blocks, A, B, N, M, D, row0, nrows, reinterpret_cast<float*>(ws + L.thr32),
+                              reinterpret_cast<double*>(ws + L.thr64),
+                              reinterpret_cast<score_key_t*>(ws + L.top1key),
+                              reinterpret_cast<float*>(ws + L.tol), rank_lo, rank_hi, resolved);
+  if (rc != CMHSE_OK) return rc;
+  LabelExactPreParams q;
+  q.A = A;
+  q.B = B;
+  q.M = M;
+  q.D = D;
+  q.row0 = row0;
+  q.nrows = nrows;
+  q.norm_a = reinterpret_cast<double*>(ws + L.norm_a);
+  q.norm_b_max = reinterpret_cast<unsigned*>(ws + L.norm_b_max);
+  q.rank_lo = rank_lo;
+  q.ties = rank_hi;
+  q.resolved = resolved;
+  q.top1key = p.top1key;
+  PairExactParams t;
+  t.A = A;
+  t.B = B;
+  t.M = M;
+  t.D = D;
+  t.row0 = row0;
+  t.nrows = nrows;
+  t.n_pairs = n_pairs;
+  t.pos_off = pos_off;
+  t.pos_idx = pos_idx;
+  t.pair64 = reinterpret_cast<double*>(ws + L.pair64);
+  t.thr64 = reinterpret_cast<double*>(ws + L.thr64);
+  t.thr32 = p.diag;
+  t.at_thr = reinterpret_cast<int32_t*>(ws + L.at_thr);
+  t.best_pos = best_pos;
+  t.best_score = best_score;
+  const int32_t scale = tunables().rank_exact_tol_scale.load(std::memory_order_relaxed);
+  constexpr int kWaves = kThreads / 64;
+  if (hipMemsetAsync(q.norm_b_max, 0, sizeof(unsigned), stream) != hipSuccess) return CMHSE_ERR_LAUNCH;
+  const int64_t pre_rows = static_cast<int64_t>(nrows) + M;
+  hipLaunchKernelGGL(label_exact_pre_kernel, dim3(static_cast<unsigned>((pre_rows + kWaves - 1) / kWaves)),
+                     dim3(kThreads), 0, stream, q);
+  hipLaunchKernelGGL(exact_tol_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream, q.norm_a,
+                     q.norm_b_max, reinterpret_cast<float*>(ws + L.tol), D, scale, nrows);
+  hipLaunchKernelGGL(pair_exact_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(n_pairs) + kWaves - 1) / kWaves)),
+                     dim3(kThreads), 0, stream, t);
+  hipLaunchKernelGGL(label_exact_reduce_kernel, dim3((nrows + kWaves - 1) / kWaves), dim3(kThreads), 0, stream, t);
+  rc = launch_tiles(sim_kernel<kSimLabelExact, true>, sim_kernel<kSimLabelExact, false>, D,
+                    dim3(static_cast<unsigned>(blocks)), TileSmem<kSimBM, kSimBN>::kBytes, stream, p);
+  if (rc != CMHSE_OK) return rc;
+  hipLaunchKernelGGL(label_exact_finalize_kernel, dim3((nrows + 255) / 256), dim3(256), 0, stream, p.top1key,
+                     rank_lo, rank_hi, t.at_thr, top1, nrows);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }
 

@@ -1256,6 +1256,96 @@ def i2t_t2i_exact(images, captions, ties='optimistic', top1='fp32'):
   return sides[0], sides[1], info
 
 
+def _check_exact_options(ties, top1):
+  if ties not in ('optimistic', 'pessimistic'):
+    raise ValueError("ties must be 'optimistic' or 'pessimistic', got %r" % (ties,))
+  if top1 not in ('fp32', 'exact'):
+    raise ValueError("top1 must be 'fp32' or 'exact', got %r" % (top1,))
+
+
+def _labelled_exact_side(q, g, csr, top1):
+  """(rank_lo, rank_hi, top1, resolved) device tensors of one direction, and the float64 columns of the
+  certified arg-max (None with top1='fp32')."""
+  lo, hi, t1, _, res = ops.sim_rank_labelled_exact(q, g, csr)
+  if top1 != 'exact':
+    return (lo, hi, t1, res), None
+  _, top, top_res = ops.sim_topk_exact(q, g, 1)
+  return (lo, hi, top.reshape(-1), res), top_res
+
+
+def _exact_side_info(host):
+  return dict(report_lo=report_from_ranks(host[0]), report_hi=report_from_ranks(host[1]),
+              tied_rows=numpy.flatnonzero(host[0] < host[1]), resolved=int(host[3].sum()))
+
+
+def rank_labelled_exact(queries, gallery, positives, ties='optimistic', top1='fp32'):
+  """rank_labelled on the ranks of the FLOAT64 scores, certified (ops.sim_rank_labelled_exact): the rank of
+  a query is the rank of its best-placed positive among the float64 scores of the same embeddings,
+  independent of summation order, tile shape and machine.  `positives` as for rank_labelled (lists may be
+  unsorted and repeat an index).  Returns (report, top1, ranks, info) with the first three in rank_labelled's
+  format; `ranks` is rank_lo for ties='optimistic' (a negative that ties the best positive exactly is not
+  counted) and rank_hi for ties='pessimistic' (it is; a positive that ties the best positive never is).
+  info = {'report_lo', 'report_hi', 'tied_rows' (the rows with rank_lo < rank_hi), 'resolved' (the columns
+  that went through float64)}, and 'top1_resolved' with top1='exact' (the arg-max of the float64 scores from
+  ops.sim_topk_exact(..., 1); the default 'fp32' is sim_rank_labelled's top1, not certified).  NumPy in,
+  NumPy out (float64), one device-to-host copy; GPU tensors in: top1 and ranks stay int32 device tensors.
+  The ranking cache i2t / t2i serve from is neither read nor changed."""
+  _check_exact_options(ties, top1)
+  on_device = isinstance(queries, torch.Tensor) and queries.is_cuda
+  csr = ops.positives_csr(positives, len(queries), len(gallery))   # argument errors before the upload
+  q = _as_device(queries)
+  dev, top_res = _labelled_exact_side(q, _as_device(gallery, q.device), csr, top1)
+  flat = torch.cat(list(dev) + ([top_res] if top_res is not None else [])).cpu().numpy()
+  n = dev[0].numel()
+  host = [x.astype(numpy.float64) for x in numpy.split(flat[:4 * n], 4)]
+  pick = 0 if ties == 'optimistic' else 1
+  info = _exact_side_info(host)
+  if top1 == 'exact':
+    info['top1_resolved'] = int(flat[4 * n:].astype(numpy.int64).sum())
+  report = info['report_lo' if pick == 0 else 'report_hi']
+  if on_device:
+    return report, dev[2], dev[pick], info
+  return report, host[2], host[pick], info
+
+
+def i2t_t2i_labelled_exact(images, captions, pairs, ties='optimistic', top1='fp32'):
+  """i2t_t2i_labelled on the ranks of the FLOAT64 scores, certified (ops.sim_rank_labelled_exact): the
+  two-annotation-set report of i2t_t2i_labelled's example with i2t_t2i_exact's guarantees and its
+  [optimistic, pessimistic] interval.  `pairs` as for i2t_t2i_labelled.  Returns
+  ((report, top1, ranks) image -> caption, the same caption -> image, info) with i2t_t2i_exact's structure
+  and keys: `ranks` is rank_lo for ties='optimistic' and rank_hi for ties='pessimistic' (every NEGATIVE that
+  ties a row's best positive exactly counts against it; another positive of the row that ties it does not:
+  two annotation sets that share a caption are not a tie); info = {'i2t': d, 't2i': d, 'resolved': total},
+  each d with 'report_lo', 'report_hi', 'tied_rows' and 'resolved'; top1='exact' makes top1 the certified
+  float64 arg-max (ops.sim_topk_exact(..., 1) per direction, counted in info['top1_resolved']).  With pairs
+  (i, i) exactly what i2t_t2i_exact returns.  NumPy arrays or GPU tensors; one device-to-host copy; GPU
+  tensors in: top1 and ranks stay int32 device tensors.  The ranking cache i2t / t2i serve from is neither
+  read nor changed."""
+  _check_exact_options(ties, top1)
+  on_device = isinstance(images, torch.Tensor) and images.is_cuda
+  csr_i, csr_t = csr_from_pairs(pairs, len(images), len(captions))   # argument errors before the upload
+  v = _as_device(images)
+  p = _as_device(captions, v.device)
+  out_i, res_i = _labelled_exact_side(v, p, csr_i, top1)
+  out_t, res_t = _labelled_exact_side(p, v, csr_t, top1)
+  n, m = out_i[0].numel(), out_t[0].numel()
+  tail = [res_i, res_t] if top1 == 'exact' else []
+  # (the two sides differ in length: one flat vector, cut on the host)
+  flat = torch.cat(list(out_i) + list(out_t) + tail).cpu().numpy()
+  host_i = [x.astype(numpy.float64) for x in numpy.split(flat[:4 * n], 4)]
+  host_t = [x.astype(numpy.float64) for x in numpy.split(flat[4 * n:4 * (n + m)], 4)]
+  pick = 0 if ties == 'optimistic' else 1
+  info, sides = {}, []
+  for name, host, dev in (('i2t', host_i, out_i), ('t2i', host_t, out_t)):
+    info[name] = _exact_side_info(host)
+    report = info[name]['report_lo' if pick == 0 else 'report_hi']
+    sides.append((report, dev[2], dev[pick]) if on_device else (report, host[2], host[pick]))
+  info['resolved'] = info['i2t']['resolved'] + info['t2i']['resolved']
+  if top1 == 'exact':
+    info['top1_resolved'] = int(flat[4 * (n + m):].astype(numpy.int64).sum())
+  return sides[0], sides[1], info
+
+
 def _rank_report(queries, gallery):
   rank, top1 = ops.sim_rank(_as_device(queries), _as_device(gallery))
   ranks = rank.cpu().numpy().astype(numpy.float64)      # the reference stores ranks in float64

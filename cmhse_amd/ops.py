@@ -1036,6 +1036,64 @@ def sim_rank_labelled(queries, gallery, positives, row0=0, nrows=None, return_sc
   return (out[0], out[1], out[2], score) if return_score else (out[0], out[1], out[2])
 
 
+def sorted_unique_csr(off, idx):
+  """The CSR labels (off [n + 1], idx) with every query's list sorted ascending and its duplicates dropped:
+  the form cmhse_sim_rank_labelled_exact requires (the same label SETS; int32 arrays).  No GPU."""
+  off = np.asarray(off, dtype=np.int64)
+  idx = np.asarray(idx, dtype=np.int64)
+  n = off.size - 1
+  if idx.size:
+    inside = np.ones(idx.size, dtype=bool)       # entry e and entry e - 1 belong to the same list
+    inside[off[:-1][off[:-1] < idx.size]] = False
+    if (idx[1:] > idx[:-1])[inside[1:]].all():   # already in that form (csr_from_pairs' lists are): no sort
+      return off.astype(np.int32), idx.astype(np.int32)
+  query = np.repeat(np.arange(n, dtype=np.int64), np.diff(off))
+  order = np.lexsort((idx, query))
+  query, idx = query[order], idx[order]
+  keep = np.ones(idx.size, dtype=bool)
+  keep[1:] = (query[1:] != query[:-1]) | (idx[1:] != idx[:-1])
+  out = np.zeros(n + 1, dtype=np.int64)
+  np.cumsum(np.bincount(query[keep], minlength=n), out=out[1:])
+  return out.astype(np.int32), idx[keep].astype(np.int32)
+
+
+def sim_rank_labelled_exact(queries, gallery, positives, row0=0, nrows=None, return_score=False):
+  """sim_rank_labelled on the FLOAT64 scores of the same fp32 rows, certified, as an interval
+  (cmhse_sim_rank_labelled_exact; `positives`: positives_csr's forms, given for ALL queries — the stripe
+  arguments slice them; lists may be unsorted and hold duplicates as for sim_rank_labelled: they are sorted
+  and de-duplicated here).  Returns int32 device tensors (rank_lo, rank_hi, top1, best_pos, resolved):
+  rank_lo[i] counts the gallery rows whose float64 score lies above that of query i's best positive,
+  rank_hi[i] adds the NEGATIVES that tie it exactly (a positive that ties the best positive is not
+  counted); top1 is sim_rank_labelled's, not certified; best_pos the best positive under float64 (the
+  smallest index on exact ties); resolved the columns of each row that went through float64 (>= 1).  With
+  return_score also thr64, the float64 score of best_pos.  The result depends on neither summation order,
+  tile shape nor machine."""
+  lib = _lib.load()
+  a = _f32c(queries, 'queries')
+  b = _f32c(gallery, 'gallery')
+  N, D = a.shape
+  M = b.shape[0]
+  if b.shape[1] != D:
+    raise ValueError('embedding widths differ')
+  off, idx = sorted_unique_csr(*positives_csr(positives, N, M, row0, nrows))
+  nrows = off.size - 1
+  out = torch.empty(5, nrows, dtype=torch.int32, device=a.device)
+  score = torch.empty(nrows, dtype=torch.float64, device=a.device) if return_score else None
+  if nrows > 0:
+    labels = np.concatenate([off, idx])          # one upload; the kernels read the device copy
+    labels_d = upload(labels, a.device)
+    ws_bytes = lib.cmhse_sim_rank_labelled_exact_workspace(nrows, idx.size)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    rc = lib.cmhse_sim_rank_labelled_exact(a.data_ptr(), b.data_ptr(), N, M, D, row0, nrows, off.ctypes.data,
+                                           idx.ctypes.data, labels_d.data_ptr(), labels_d.data_ptr() + 4 * off.size,
+                                           idx.size, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                           out[3].data_ptr(), score.data_ptr() if return_score else None,
+                                           out[4].data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+    _lib.check(rc, 'cmhse_sim_rank_labelled_exact')
+  res = (out[0], out[1], out[2], out[3], out[4])
+  return res + (score,) if return_score else res
+
+
 _GROUP_REDUCE = {'max': _lib.GROUP_MAX, 'mean': _lib.GROUP_MEAN}
 
 

@@ -426,6 +426,64 @@ int cmhse_sim_rank_exact(const float* A, const float* B, int32_t N, int32_t M, i
                          int32_t* top1 /*[nrows]*/, int32_t* resolved /*[nrows]*/, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* Certified labelled ranking: cmhse_sim_rank_exact's interval for cmhse_sim_rank_labelled's protocol — the
+ * ranks of the FLOAT64 scores against any set of positives per query, any gallery size.  Queries A [N,D],
+ * gallery B [M,D], N and M independent, the stripe [row0, row0+nrows).  Labels are CSR relative to the stripe,
+ * passed as a host copy and a device copy, exactly as cmhse_sim_rank_labelled takes them, with ONE stricter
+ * rule: the list of every query must be STRICTLY ASCENDING (sorted, no duplicate), else CMHSE_ERR_ARG — the
+ * pessimistic rank needs the number of DISTINCT positives at the threshold (ops.sim_rank_labelled_exact sorts
+ * and de-duplicates for its callers).
+ * s64(i,j) is the float64 dot product of cmhse_sim_rank_exact: the ONE routine, its lane order and its
+ * butterfly, for every float64 score of the call, the thresholds included.  With P_i the list of query i and
+ * thr64(i) = max over p in P_i of s64(i,p), all outputs [nrows]:
+ *   rank_lo[i - row0]    = #{ j in [0,M) : s64(i,j) > thr64(i) }   cmhse_sim_rank_labelled's optimistic rule
+ *                          on the float64 scores;
+ *   rank_hi[i - row0]    = rank_lo + #{ j not in P_i : s64(i,j) == thr64(i) }   the position of the best-placed
+ *                          positive if every exact tie with a NEGATIVE goes against it; a positive that ties
+ *                          the best positive is never counted.  Above rank_lo only on exact float64 ties (a
+ *                          collapsed model: rank_lo 0, rank_hi M - |P_i|);
+ *   top1[i - row0]       = cmhse_sim_rank_labelled's, by its fp32 rule, unchanged and NOT certified (the
+ *                          certified arg-max is cmhse_sim_topk_exact with K = 1);
+ *   best_pos[i - row0]   = the p in P_i with s64(i,p) == thr64(i), the smallest such p;
+ *   best_score[i - row0] = thr64(i), float64 (may be NULL);
+ *   resolved[i - row0]   = the columns of row i that went through float64 in the counting pass: a diagnostic,
+ *                          a function of the inputs alone, >= 1 (the best positive's own column always lies
+ *                          inside the tolerance).
+ * How: (1) one wave per row of the stripe and of B: |a_i|, zeroed counters, max_j |b_j|, then tol_i = 2 E_i
+ * (1 + 2^-18) rounded up to fp32, the tolerance of cmhse_sim_rank_exact; (2) the float64 threshold pass: one
+ * wave per (query, positive) pair writes its s64 into a vector of n_pairs doubles, then one wave per query
+ * reduces its list to thr64, best_pos and the number of list entries at thr64 — no floating-point atomics,
+ * nothing that depends on who arrives first; (3) the counting pass of cmhse_sim_rank_exact, no column excluded,
+ * against thr32(i) = float(thr64(i)): fl(v(i,j) - thr32(i)) > tol_i: surely above; < -tol_i: surely below;
+ * anything else is recomputed as s64(i,j) and compared with thr64(i) inside the tile that found it.  The
+ * tolerance is valid unchanged because |thr32 - thr64| <= u |thr64| (or 2^-150) <= E_i takes the place of the
+ * diagonal's |v(i,i) - s64(i,i)| <= E_i (derived in sim.hip); (4) rank_hi = rank_lo + ties - (list entries at
+ * thr64), and top1 is decoded.
+ * Properties: the results do not depend on the tolerance as long as it is valid (the tunable
+ * "rank_exact_tol_scale" only moves `resolved`), nor on tiling, scheduling or math mode; query stripes, with
+ * their labels sliced, concatenate bit for bit into the whole call; with M >= N and P_i = {i}, rank_lo and
+ * rank_hi equal cmhse_sim_rank_exact's.  Inputs are assumed finite; D < 2^24 (CMHSE_ERR_UNSUPPORTED otherwise).
+ * Errors, before anything is launched, with the codes and in the order of cmhse_sim_rank_labelled:
+ * CMHSE_ERR_ARG for a null A / B; N, M or D <= 0; a stripe outside [0, N]; (nrows == 0 with n_pairs == 0:
+ * nothing is launched and every pointer but A and B may be NULL; nrows == 0 with other n_pairs: CMHSE_ERR_ARG;)
+ * a null label pointer or n_pairs < nrows; pos_off_host[0] != 0, pos_off_host[nrows] != n_pairs, a prefix sum
+ * that does not increase (an empty list); an index outside [0, M); a list that is not strictly ascending; a
+ * null rank_lo / rank_hi / top1 / best_pos / resolved / workspace.  Then CMHSE_ERR_WORKSPACE for a workspace
+ * that is unaligned (256 bytes) or smaller than cmhse_sim_rank_labelled_exact_workspace(nrows, n_pairs), then
+ * CMHSE_ERR_UNSUPPORTED for D >= 2^24.
+ * cmhse_sim_rank_labelled_exact_workspace(nrows, n_pairs): 0 for nrows <= 0 or n_pairs < nrows; otherwise
+ * about 36 bytes a row AND 8 bytes a pair — unlike cmhse_sim_rank_labelled's it grows with n_pairs (the
+ * float64 score of every pair is kept for the deterministic reduction).
+ * Cost: cmhse_sim_rank_exact's without its diagonal pass, plus one wave-wide float64 dot product per pair. */
+size_t cmhse_sim_rank_labelled_exact_workspace(int32_t nrows, int32_t n_pairs);
+int cmhse_sim_rank_labelled_exact(const float* A, const float* B, int32_t N, int32_t M, int32_t D, int32_t row0,
+                                  int32_t nrows, const int32_t* pos_off_host, const int32_t* pos_idx_host,
+                                  const int32_t* pos_off, const int32_t* pos_idx, int32_t n_pairs,
+                                  int32_t* rank_lo /*[nrows]*/, int32_t* rank_hi /*[nrows]*/,
+                                  int32_t* top1 /*[nrows]*/, int32_t* best_pos /*[nrows]*/,
+                                  double* best_score /*[nrows] or NULL*/, int32_t* resolved /*[nrows]*/,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* Certified top-K retrieval: the K best columns of every row by the FLOAT64 scores of the same fp32 rows, at
  * about twice the cost of cmhse_sim_topk.  A [N,D] queries, B [M,D] gallery, N and M independent (no diagonal
  * convention), the stripe [row0, row0+nrows).  s64(i,j) is the float64 dot product of cmhse_sim_rank_exact:
