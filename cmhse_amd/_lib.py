@@ -142,6 +142,12 @@ SIGNATURES = {
     'cmhse_group_rank': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                         c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cmhse_group_rank_exact_workspace': (c_size_t, [c_int32, c_int32, c_int32]),
+    'cmhse_group_rank_exact_tolerance': (ctypes.c_double, [c_int32, c_int32, ctypes.c_double, ctypes.c_double]),
+    'cmhse_group_rank_exact': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                              c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_size_t, c_void_p]),
     'cmhse_group_topk_plan': (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                         c_int32]),
     'cmhse_group_topk_workspace': (c_size_t, [c_void_p, c_int32]),

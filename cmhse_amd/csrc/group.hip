@@ -22,6 +22,12 @@
 //                       (score_tile.hpp's score key), one partial per tile;
 //   group_rank_final_kernel   sums / maxes the partials of each row and column.
 //
+// Certified group-wise ranking (cmhse_group_rank_exact: the ranks of the float64 block scores):
+//   group_exact_pre_kernel / group_exact_tol_kernel / group_exact_diag_kernel   norms, tolerances, G64[i, i];
+//   group_rank_exact_kernel   group_rank_kernel's tiles with a tolerance per query; the undecided blocks go
+//                             through block64 (exact64.hpp) before the workgroup leaves;
+//   group_rank_exact_final_kernel   the partials, rank_hi, top-1.
+//
 // Group-wise top-K (cmhse_group_topk: any video set against any paragraph set, either way round):
 //   cmhse_group_topk_plan     host only: the gallery side packed as above, the query side also capped
 //                             at gt_qcap(K) groups a tile (the LDS of its lists);
@@ -35,6 +41,8 @@
 #include <stdint.h>
 
 #include "../../include/cmhse_hip.h"
+#include "exact64.hpp"
+#include "gru_ws.hpp"
 #include "nt_core.hpp"
 #include "score_tile.hpp"
 #include "topk_lists.hpp"
@@ -395,6 +403,245 @@ __global__ void group_rank_final_kernel(const GroupRankParams p) {
   (col ? p.top1_p2v : p.top1_v2p)[i] = top1;
 }
 
+// ---- certified group-wise ranking (cmhse_group_rank_exact) ------------------------------------------
+// The ranks of the FLOAT64 block scores G64 (exact64.hpp: block64, its bound and its tolerance) at the cost of
+// cmhse_group_rank: group_sim_kernel's fp32 G decides every comparison whose difference exceeds the certified
+// tolerance of its row (video -> paragraph) or column (paragraph -> video); the others are recomputed with
+// block64 inside the G tile that found them.
+//   group_exact_pre_kernel    one wave per clip / caption row: its norm sqrt(dot64(x, x)), and the largest norm
+//                             of each side (rounded up to fp32, atomic max on the bits);
+//   group_exact_tol_kernel    per video i: A_i and tol_v2p[i]; per paragraph j: B_j and tol_p2v[j]; the call's
+//                             counters zeroed;
+//   group_exact_diag_kernel   one wave per group: G64[i, i];
+//   group_rank_exact_kernel   group_rank_kernel's tiles, two compares per element and direction, and the
+//                             resolve step;
+//   group_rank_exact_final_kernel   the partials, rank_hi = rank_lo + ties, top1 decoded.
+struct GroupExactParams {
+  const float* C;          // [Nc, D] clip rows
+  const float* S;          // [Ns, D] caption rows
+  int32_t D, B, Nc, Ns, use_max, scale;
+  const int32_t* clip_off; // [B + 1] (device copy of the plan)
+  const int32_t* cap_off;  // [B + 1]
+  double* norm_c;          // [Nc]
+  double* norm_s;          // [Ns]
+  unsigned* norm_max;      // [0]: bits of the largest clip norm, [1]: of the largest caption norm (zeroed)
+  double* d64;             // [B] G64[i, i]
+  float* tol_v2p;          // [B]
+  float* tol_p2v;          // [B]
+  // rank_lo: the float64 "above" counts until the last launch adds the fp32 ones; rank_hi: the float64 ties
+  int32_t *lo_v2p, *hi_v2p, *res_v2p, *lo_p2v, *hi_p2v, *res_p2v;
+};
+
+__global__ __launch_bounds__(kThreads) void group_exact_pre_kernel(const GroupExactParams p) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6);
+  if (r >= static_cast<int64_t>(p.Nc) + p.Ns) return;   // (wave-uniform)
+  const bool cap = r >= p.Nc;
+  const float* x = cap ? p.S + (r - p.Nc) * p.D : p.C + r * p.D;
+  const float* const xs[1] = {x};
+  double xx[1];
+  dot64_wide<1, 8>(x, xs, p.D, lane, xx);   // (dot64(x, x)'s bits, eight loads in flight)
+  const double n = sqrt(xx[0]);
+  if (lane == 0) {
+    (cap ? p.norm_s[r - p.Nc] : p.norm_c[r]) = n;
+    atomicMax(p.norm_max + (cap ? 1 : 0), __float_as_uint(round_up_f32(n)));
+  }
+}
+
+// thread t < B: video t; B <= t < 2B: paragraph t - B (every group has 1 .. 128 rows: the plan is checked)
+__global__ void group_exact_tol_kernel(const GroupExactParams p) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * p.B) return;
+  const bool par = t >= p.B;
+  const int g = par ? t - p.B : t;
+  const int32_t* off = par ? p.cap_off : p.clip_off;
+  const double* norm = par ? p.norm_s : p.norm_c;
+  double mine = 0.0;
+  for (int r = off[g]; r < off[g + 1]; ++r) mine = norm[r] > mine ? norm[r] : mine;
+  const double other = static_cast<double>(__uint_as_float(p.norm_max[par ? 0 : 1]));
+  (par ? p.tol_p2v : p.tol_v2p)[g] =
+      round_up_f32(group_exact_tolerance(p.D, p.use_max != 0, mine, other) * static_cast<double>(p.scale));
+  (par ? p.lo_p2v : p.lo_v2p)[g] = 0;
+  (par ? p.hi_p2v : p.hi_v2p)[g] = 0;
+  (par ? p.res_p2v : p.res_v2p)[g] = 0;
+}
+
+__global__ __launch_bounds__(kThreads) void group_exact_diag_kernel(const GroupExactParams p) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (i >= p.B) return;   // (wave-uniform)
+  const double g = block64(p.C, p.S, p.D, p.clip_off[i], p.clip_off[i + 1], p.cap_off[i], p.cap_off[i + 1],
+                           p.use_max != 0, lane);
+  if (lane == 0) p.d64[i] = g;
+}
+
+// wave_rank64 with a tolerance: the count of x surely above d, the mask of the undecided x, the top-1 key
+__device__ __forceinline__ void wave_rank64_exact(float x, bool valid, bool self, float d, float tol, int idx0,
+                                                  int* cnt, unsigned long long* amb, score_key_t* key) {
+  // surely above: fl(x - d) > tol; surely below: fl(d - x) = -fl(x - d) > tol; else undecided (tol >= 0, finite
+  // inputs: the difference is no NaN)
+  const float diff = x - d;
+  const bool mine = valid && !self;
+  const unsigned long long gt = __ballot(mine && diff > tol);
+  *amb = __ballot(mine && fabsf(diff) <= tol);
+  const unsigned ob = valid ? ordered_bits(x) : 0u;
+  unsigned obmax = ob;
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    const unsigned o = __shfl_xor(obmax, s, 64);
+    obmax = o > obmax ? o : obmax;
+  }
+  const unsigned long long eq = __ballot(valid && ob == obmax);
+  const int best = idx0 + (__ffsll(static_cast<long long>(eq)) - 1);
+  *cnt = __popcll(gt);
+  *key = bits_key(obmax, best);
+}
+
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long x) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(x));
+  const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(x >> 32));
+  return (static_cast<unsigned long long>(hi) << 32) | lo;
+}
+
+struct GroupRankExactParams {
+  GroupRankParams r;       // G, the partials (cnt: the fp32-decided "above" counts), top1_*; rank_* unused
+  GroupExactParams e;
+};
+
+// group_rank_kernel's tile and partials.  s_arow[r] holds the undecided columns of tile row r for the query
+// "video i0 + r" (bit = tile column), s_acol[c] the undecided rows of tile column c for the query "paragraph
+// j0 + c" (bit = tile row); every word is written before the barrier.  The resolve step: wave w takes the tile
+// rows w, w + 4, ...; for row r the blocks either direction wants are the union of s_arow[r] and bit r of the 64
+// s_acol words, each computed ONCE by block64 and compared with G64[i, i] and / or G64[j, j].  The barrier is
+// reached by every thread, the loops are bounded by the tile's 64 rows and 64 bits, nothing waits on another
+// workgroup, and the sums are integer atomics: they do not depend on who adds first.
+__global__ __launch_bounds__(kThreads) void group_rank_exact_kernel(const GroupRankExactParams pp) {
+  const GroupRankParams& p = pp.r;
+  const GroupExactParams& q = pp.e;
+  __shared__ float s[kGrRankT][kGrRankT + 1];
+  __shared__ float s_drow[kGrRankT], s_dcol[kGrRankT], s_trow[kGrRankT], s_tcol[kGrRankT];
+  __shared__ unsigned long long s_arow[kGrRankT], s_acol[kGrRankT];
+  __shared__ int s_any;
+  const int it = blockIdx.x / p.tiles, jt = blockIdx.x % p.tiles;
+  const int i0 = it * kGrRankT, j0 = jt * kGrRankT;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t B = p.B;
+  for (int e = tid; e < kGrRankT * kGrRankT; e += kThreads) {
+    const int r = e / kGrRankT, c = e % kGrRankT;
+    s[r][c] = (i0 + r < p.B && j0 + c < p.B) ? p.G[(i0 + r) * B + j0 + c] : 0.f;
+  }
+  if (tid < kGrRankT) {
+    const int i = i0 + tid;
+    s_drow[tid] = i < p.B ? p.G[i * (B + 1)] : 0.f;
+    s_trow[tid] = i < p.B ? q.tol_v2p[i] : 0.f;
+  } else if (tid < 2 * kGrRankT) {
+    const int j = j0 + tid - kGrRankT;
+    s_dcol[tid - kGrRankT] = j < p.B ? p.G[j * (B + 1)] : 0.f;
+    s_tcol[tid - kGrRankT] = j < p.B ? q.tol_p2v[j] : 0.f;
+  } else if (tid == 2 * kGrRankT) {
+    s_any = 0;
+  }
+  __syncthreads();
+  constexpr int kPerWave = kGrRankT / (kThreads / 64);
+  for (int k = 0; k < kPerWave; ++k) {
+    const int rr = wave * kPerWave + k;
+    int cnt;
+    unsigned long long amb;
+    score_key_t key;
+    // row i = i0 + rr against the tile's 64 columns (lane = column)
+    if (i0 + rr < p.B) {   // (wave-uniform)
+      const int j = j0 + lane;
+      wave_rank64_exact(s[rr][lane], j < p.B, j == i0 + rr, s_drow[rr], s_trow[rr], j0, &cnt, &amb, &key);
+      if (lane == 0) {
+        p.cnt_row[jt * B + i0 + rr] = cnt;
+        p.key_row[jt * B + i0 + rr] = key;
+      }
+    } else {
+      amb = 0ull;
+    }
+    if (lane == 0) {
+      s_arow[rr] = amb;
+      if (amb != 0ull) s_any = 1;
+    }
+    // column j = j0 + rr against the tile's 64 rows (lane = row)
+    if (j0 + rr < p.B) {
+      const int i = i0 + lane;
+      wave_rank64_exact(s[lane][rr], i < p.B, i == j0 + rr, s_dcol[rr], s_tcol[rr], i0, &cnt, &amb, &key);
+      if (lane == 0) {
+        p.cnt_col[it * B + j0 + rr] = cnt;
+        p.key_col[it * B + j0 + rr] = key;
+      }
+    } else {
+      amb = 0ull;
+    }
+    if (lane == 0) {
+      s_acol[rr] = amb;
+      if (amb != 0ull) s_any = 1;
+    }
+  }
+  __syncthreads();
+  if (s_any == 0) return;   // (workgroup-uniform: every thread reads the same word, past the last barrier)
+  const bool use_max = q.use_max != 0;
+  for (int r = wave; r < kGrRankT; r += kThreads / 64) {
+    // (rows and columns past B set no bit; both masks are wave-uniform, and held in scalar registers)
+    const unsigned long long rbits = uniform64(s_arow[r]);
+    const unsigned long long cbits = __ballot((s_acol[lane] >> r) & 1ull);
+    unsigned long long bits = rbits | cbits;
+    if (bits == 0ull) continue;
+    const int i = i0 + r;
+    const int r_begin = q.clip_off[i], r_end = q.clip_off[i + 1];
+    const double dii = q.d64[i];
+    int above = 0, equal = 0, n = 0;
+    while (bits != 0ull) {
+      const int c = __ffsll(static_cast<long long>(bits)) - 1;
+      bits &= bits - 1ull;
+      const int j = j0 + c;
+      const double g = block64(q.C, q.S, q.D, r_begin, r_end, q.cap_off[j], q.cap_off[j + 1], use_max, lane);
+      if ((rbits >> c) & 1ull) {   // query: video i, its row of G
+        above += g > dii;
+        equal += g == dii;
+        ++n;
+      }
+      if (((cbits >> c) & 1ull) && lane == 0) {   // query: paragraph j, its column of G
+        const double djj = q.d64[j];
+        if (g > djj) atomicAdd(&q.lo_p2v[j], 1);
+        if (g == djj) atomicAdd(&q.hi_p2v[j], 1);
+        atomicAdd(&q.res_p2v[j], 1);
+      }
+    }
+    if (lane == 0 && n != 0) {
+      if (above) atomicAdd(&q.lo_v2p[i], above);
+      if (equal) atomicAdd(&q.hi_v2p[i], equal);
+      atomicAdd(&q.res_v2p[i], n);
+    }
+  }
+}
+
+// thread t < B: row t (video -> paragraph); B <= t < 2B: column t - B (paragraph -> video).  rank_lo arrives
+// holding the float64-decided "above" count, rank_hi the float64 ties.
+__global__ void group_rank_exact_final_kernel(const GroupRankExactParams pp) {
+  const GroupRankParams& p = pp.r;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * p.B) return;
+  const bool col = t >= p.B;
+  const int i = col ? t - p.B : t;
+  const int32_t* cnt = col ? p.cnt_col : p.cnt_row;
+  const score_key_t* key = col ? p.key_col : p.key_row;
+  int c = 0;
+  score_key_t k = 0;
+  for (int q = 0; q < p.tiles; ++q) {
+    const int64_t e = static_cast<int64_t>(q) * p.B + i;
+    c += cnt[e];
+    k = key[e] > k ? key[e] : k;
+  }
+  int32_t* lo = col ? pp.e.lo_p2v : pp.e.lo_v2p;
+  int32_t* hi = col ? pp.e.hi_p2v : pp.e.hi_v2p;
+  const int32_t rank_lo = lo[i] + c;
+  lo[i] = rank_lo;
+  hi[i] += rank_lo;
+  (col ? p.top1_p2v : p.top1_v2p)[i] = key_index(k);
+}
+
 // prefix sums of B >= 1 positive counts, Nc / Ns at the end
 bool offsets_ok(const int32_t* off, int32_t B) {
   if (off[0] != 0) return false;
@@ -616,6 +863,111 @@ extern "C" int cmhse_group_rank(const float* clips, const float* caps, int32_t N
   if (rc != CMHSE_OK) return rc;
   hipLaunchKernelGGL(group_rank_kernel, dim3(static_cast<unsigned>(tiles * tiles)), dim3(kThreads), 0, stream, rp);
   hipLaunchKernelGGL(group_rank_final_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, stream, rp);
+  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
+}
+
+namespace {
+// cmhse_group_rank's regions first (G, the partials), then the O(B + Nc + Ns) vectors of the certified call
+struct GroupExactWs {
+  size_t d64, tol_v2p, tol_p2v, norm_c, norm_s, norm_max, total;
+};
+GroupExactWs group_exact_ws(int32_t B, int32_t Nc, int32_t Ns) {
+  GroupExactWs L;
+  size_t off = cmhse_group_rank_workspace(B);
+  L.d64 = off, off += align256(static_cast<size_t>(B) * sizeof(double));
+  L.tol_v2p = off, off += align256(static_cast<size_t>(B) * sizeof(float));
+  L.tol_p2v = off, off += align256(static_cast<size_t>(B) * sizeof(float));
+  L.norm_c = off, off += align256(static_cast<size_t>(Nc) * sizeof(double));
+  L.norm_s = off, off += align256(static_cast<size_t>(Ns) * sizeof(double));
+  L.norm_max = off, off += 256;
+  L.total = off;
+  return L;
+}
+}  // namespace
+
+extern "C" size_t cmhse_group_rank_exact_workspace(int32_t B, int32_t Nc, int32_t Ns) {
+  if (B <= 0 || Nc < B || Ns < B) return 0;   // (every group has a row)
+  return group_exact_ws(B, Nc, Ns).total;
+}
+
+extern "C" double cmhse_group_rank_exact_tolerance(int32_t D, int32_t reduce, double norm_a, double norm_b_max) {
+  if (D <= 0 || !(norm_a >= 0.0) || !(norm_b_max >= 0.0)) return NAN;
+  if (reduce != CMHSE_GROUP_MAX && reduce != CMHSE_GROUP_MEAN) return NAN;
+  return group_exact_tolerance(D, reduce == CMHSE_GROUP_MAX, norm_a, norm_b_max);
+}
+
+extern "C" int cmhse_group_rank_exact(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                                      int32_t B, const int32_t* plan_host, const int32_t* plan, int32_t plan_len_,
+                                      int32_t reduce, int32_t* rank_lo_v2p, int32_t* rank_hi_v2p, int32_t* top1_v2p,
+                                      int32_t* resolved_v2p, int32_t* rank_lo_p2v, int32_t* rank_hi_p2v,
+                                      int32_t* top1_p2v, int32_t* resolved_p2v, void* workspace,
+                                      size_t workspace_bytes, void* stream_) {
+  if (!rank_lo_v2p || !rank_hi_v2p || !top1_v2p || !resolved_v2p || !rank_lo_p2v || !rank_hi_p2v || !top1_p2v ||
+      !resolved_p2v || !workspace || !group_args_ok(clips, caps, Nc, Ns, D, B, plan_host, plan, plan_len_, reduce))
+    return CMHSE_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
+      workspace_bytes < cmhse_group_rank_exact_workspace(B, Nc, Ns))
+    return CMHSE_ERR_WORKSPACE;
+  const int32_t tiles = (B + kGrRankT - 1) / kGrRankT;
+  if (static_cast<int64_t>(tiles) * tiles > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  if (D >= (1 << 24)) return CMHSE_ERR_UNSUPPORTED;   // (the bound needs D u < 1)
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char* const base = static_cast<char*>(workspace);
+  char* ws = base;
+  GroupRankExactParams pp;
+  GroupRankParams& rp = pp.r;
+  rp.G = reinterpret_cast<float*>(ws);
+  ws += align256(static_cast<size_t>(B) * static_cast<size_t>(B) * sizeof(float));
+  const size_t part = static_cast<size_t>(tiles) * static_cast<size_t>(B);
+  rp.cnt_row = reinterpret_cast<int32_t*>(ws);
+  ws += align256(part * sizeof(int32_t));
+  rp.key_row = reinterpret_cast<score_key_t*>(ws);
+  ws += align256(part * sizeof(score_key_t));
+  rp.cnt_col = reinterpret_cast<int32_t*>(ws);
+  ws += align256(part * sizeof(int32_t));
+  rp.key_col = reinterpret_cast<score_key_t*>(ws);
+  rp.B = B;
+  rp.tiles = tiles;
+  rp.rank_v2p = nullptr;
+  rp.rank_p2v = nullptr;
+  rp.top1_v2p = top1_v2p;
+  rp.top1_p2v = top1_p2v;
+  const GroupExactWs L = group_exact_ws(B, Nc, Ns);
+  GroupExactParams& q = pp.e;
+  q.C = clips;
+  q.S = caps;
+  q.D = D;
+  q.B = B;
+  q.Nc = Nc;
+  q.Ns = Ns;
+  q.use_max = reduce == CMHSE_GROUP_MAX;
+  q.scale = tunables().rank_exact_tol_scale.load(std::memory_order_relaxed);
+  q.clip_off = plan + kGrHdr;
+  q.cap_off = q.clip_off + B + 1;
+  q.norm_c = reinterpret_cast<double*>(base + L.norm_c);
+  q.norm_s = reinterpret_cast<double*>(base + L.norm_s);
+  q.norm_max = reinterpret_cast<unsigned*>(base + L.norm_max);
+  q.d64 = reinterpret_cast<double*>(base + L.d64);
+  q.tol_v2p = reinterpret_cast<float*>(base + L.tol_v2p);
+  q.tol_p2v = reinterpret_cast<float*>(base + L.tol_p2v);
+  q.lo_v2p = rank_lo_v2p;
+  q.hi_v2p = rank_hi_v2p;
+  q.res_v2p = resolved_v2p;
+  q.lo_p2v = rank_lo_p2v;
+  q.hi_p2v = rank_hi_p2v;
+  q.res_p2v = resolved_p2v;
+  constexpr int kWaves = kThreads / 64;
+  if (hipMemsetAsync(q.norm_max, 0, 2 * sizeof(unsigned), stream) != hipSuccess) return CMHSE_ERR_LAUNCH;
+  const int64_t pre_rows = static_cast<int64_t>(Nc) + Ns;
+  hipLaunchKernelGGL(group_exact_pre_kernel, dim3(static_cast<unsigned>((pre_rows + kWaves - 1) / kWaves)),
+                     dim3(kThreads), 0, stream, q);
+  hipLaunchKernelGGL(group_exact_tol_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, stream, q);
+  const int rc = launch_group_sim(clips, caps, D, B, plan_host, plan, reduce, const_cast<float*>(rp.G), stream);
+  if (rc != CMHSE_OK) return rc;
+  hipLaunchKernelGGL(group_exact_diag_kernel, dim3((B + kWaves - 1) / kWaves), dim3(kThreads), 0, stream, q);
+  hipLaunchKernelGGL(group_rank_exact_kernel, dim3(static_cast<unsigned>(tiles * tiles)), dim3(kThreads), 0, stream,
+                     pp);
+  hipLaunchKernelGGL(group_rank_exact_final_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, stream, pp);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }
 

@@ -1087,6 +1087,38 @@ def group_i2t_t2i(clip_embs, cap_embs, num_clips, num_caps=None, reduce='max'):
           (report_from_ranks(host[2]), host[3], host[2]))
 
 
+def group_i2t_t2i_exact(clip_embs, cap_embs, num_clips, num_caps=None, reduce='max', ties='optimistic'):
+  """group_i2t_t2i on the ranks of the FLOAT64 block scores, certified (ops.group_rank_exact): independent of
+  summation order, tile shape and machine, where the fp32 group ranks differ from a float64 ranking of the
+  same rows wherever captions are shared or clips nearly repeat.  Returns ((report, top1, ranks) video ->
+  paragraph, the same paragraph -> video, info), the first two in group_i2t_t2i's format; `ranks` is rank_lo
+  for ties='optimistic' (a group that ties the query's own exactly is not counted: group_i2t_t2i's rule) and
+  rank_hi for ties='pessimistic' (it is: a model that collapses the low level reports the last rank, not the
+  first).  info = {'v2p': d, 'p2v': d, 'resolved': total}, each d with 'report_lo', 'report_hi', 'tied_rows'
+  (the queries with rank_lo < rank_hi) and 'resolved' (the blocks that went through float64).  top1 is
+  group_i2t_t2i's, not certified.  NumPy in: NumPy out (float64) with one device-to-host copy; GPU tensors in:
+  top1 and ranks stay int32 device tensors.  The ranking cache i2t / t2i serve from is neither read nor
+  changed."""
+  if ties not in ('optimistic', 'pessimistic'):
+    raise ValueError("ties must be 'optimistic' or 'pessimistic', got %r" % (ties,))
+  if reduce not in ('max', 'mean'):
+    raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
+  on_device = isinstance(clip_embs, torch.Tensor) and clip_embs.is_cuda
+  ops.group_plan(num_clips, num_caps, len(clip_embs), len(cap_embs))   # argument errors before the upload
+  c = _as_device(clip_embs)
+  s = _as_device(cap_embs, c.device)
+  out = ops.group_rank_exact(c, s, num_clips, num_caps, reduce)
+  host = torch.stack(out).cpu().numpy().astype(numpy.float64)
+  pick = 0 if ties == 'optimistic' else 1
+  info, sides = {}, []
+  for name, h, dev in (('v2p', host[:4], out[:4]), ('p2v', host[4:], out[4:])):
+    info[name] = _exact_side_info(h)
+    report = info[name]['report_lo' if pick == 0 else 'report_hi']
+    sides.append((report, dev[2], dev[pick]) if on_device else (report, h[2], h[pick]))
+  info['resolved'] = info['v2p']['resolved'] + info['p2v']['resolved']
+  return sides[0], sides[1], info
+
+
 def group_retrieve(clip_embs, cap_embs, num_clips, num_caps=None, k=10, direction='p2v', reduce='max'):
   """Top-k retrieval by the group-wise score of the low level (group_i2t_t2i's score: block max of
   the clip x caption scores of a (video, paragraph) pair with max_violation, block mean without):

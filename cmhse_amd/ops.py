@@ -1188,6 +1188,28 @@ def group_rank(clips, caps, num_clips, num_caps=None, reduce='max'):
   return out[0], out[1], out[2], out[3]
 
 
+def group_rank_exact(clips, caps, num_clips, num_caps=None, reduce='max'):
+  """The ranks of the FLOAT64 block scores of group_rank's inputs, certified (cmhse_group_rank_exact):
+  (rank_lo_v2p, rank_hi_v2p, top1_v2p, resolved_v2p, rank_lo_p2v, rank_hi_p2v, top1_p2v, resolved_p2v)
+  int32 [B] device tensors on the current stream.  The float64 score of a (video, paragraph) block is the
+  maximum ('max') or the sequential clip-major float64 mean ('mean') of the float64 dot products of its
+  rows; rank_lo counts the groups strictly above the query's own (group_rank's rule), rank_hi those at or
+  above it (they differ only on exact float64 ties: bit-identical groups); top1 is group_rank's, not
+  certified; resolved the blocks of each query that fp32 could not decide and float64 did.  The result
+  depends on neither summation order, tile shape nor machine."""
+  lib = _lib.load()
+  c, s, plan, plan_d = _group_args(clips, caps, num_clips, num_caps, reduce)
+  B = int(plan[0])
+  out = torch.empty(8, B, dtype=torch.int32, device=c.device)
+  ws_bytes = lib.cmhse_group_rank_exact_workspace(B, c.shape[0], s.shape[0])
+  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=c.device)
+  rc = lib.cmhse_group_rank_exact(c.data_ptr(), s.data_ptr(), c.shape[0], s.shape[0], c.shape[1], B,
+                                  plan.ctypes.data, plan_d.data_ptr(), plan.size, _GROUP_REDUCE[reduce],
+                                  *([out[k].data_ptr() for k in range(8)] + [ws.data_ptr(), ws_bytes, _stream()]))
+  _lib.check(rc, 'cmhse_group_rank_exact')
+  return tuple(out[k] for k in range(8))
+
+
 _GROUP_DIRECTION = {'p2v': _lib.GROUP_P2V, 'v2p': _lib.GROUP_V2P}
 
 

@@ -573,6 +573,57 @@ int cmhse_group_rank(const float* clips, const float* caps, int32_t Nc, int32_t 
                      int32_t reduce, int32_t* rank_v2p, int32_t* top1_v2p, int32_t* rank_p2v,
                      int32_t* top1_p2v, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Certified group-wise ranking: the ranks of the FLOAT64 block scores of the same fp32 rows, as an interval, at
+ * about the cost of cmhse_group_rank.  Inputs as for cmhse_group_rank (counts 1..128 rows, num_caps != num_clips
+ * allowed, both reduce modes).
+ * G64(i, j), THE float64 block score — one device routine (exact64.hpp: block64) serves every float64 group
+ * score of the call, the diagonal's included:
+ *   s64(r, c) = the float64 dot product of cmhse_sim_rank_exact (dot64: its lane order, its butterfly) of clip
+ *               row r of video i and caption row c of paragraph j, rows ascending;
+ *   CMHSE_GROUP_MAX   G64 = max s64(r, c): nothing is rounded, so the order does not matter;
+ *   CMHSE_GROUP_MEAN  acc = 0.0; for r: for c: acc += s64(r, c) — sequential float64, clip-major then caption,
+ *                     the order of cmhse_group_scores' fp32 mean — then G64 = acc / double(count).
+ * Consequence: two bit-identical groups with their rows in the same order have bit-identical G64 against
+ * anything, so they tie exactly.  Under CMHSE_GROUP_MEAN a paragraph whose captions are permuted need not
+ * (float64 addition does not associate), nor need groups of equal rows but different counts.
+ * Outputs, all int32 [B]; v2p: query = video i, its row of G64; p2v: query = paragraph j, its column:
+ *   rank_lo[q]  = #{ k != q : G64(line q)[k] >  G64[q, q] }   the optimistic rule of cmhse_group_rank;
+ *   rank_hi[q]  = #{ k != q : G64(line q)[k] >= G64[q, q] }   above rank_lo only on exact float64 ties (a
+ *                 collapsed model of equal groups has rank_lo 0 and rank_hi B - 1 everywhere);
+ *   top1[q]     = cmhse_group_rank's fp32 arg-max, unchanged and NOT certified;
+ *   resolved[q] = the off-diagonal blocks of that query whose comparison went through float64: a function of
+ *                 the input (and the tunable below) alone.
+ * How: cmhse_group_rank's launches with a tolerance per query.  With E(|a|, |b|) the bound of
+ * cmhse_sim_rank_exact on |v - s64| for one fp32 MFMA score, A_i the largest clip norm of video i and Bmax the
+ * largest caption norm of the call: |G32[i,j] - G64(i,j)| <= E(A_i, Bmax) under max (a maximum is 1-Lipschitz and
+ * rounds nothing), and E plus (u + 2^-38) A_i Bmax under mean (the two float64 summations of at most 2^14 terms
+ * and the rounding of the mean to fp32); p2v swaps the roles (B_j, the largest clip norm of the call).  The
+ * tolerance is twice that, times 1 + 2^-18, rounded up to fp32 (derived in exact64.hpp).  A difference from the
+ * diagonal score beyond it decides the float64 comparison; every other block — two blocks that tie exactly
+ * among them — is recomputed with block64 inside the 64 x 64 tile of G that found it, once even when both
+ * directions want it (no list of pairs, no capacity, no retry).
+ * Properties: the results do not depend on the tolerance as long as it is valid ("rank_exact_tol_scale"
+ * multiplies it here too and only moves `resolved`; at 2^20 and D >= 16 every off-diagonal block goes through
+ * float64), nor on tiling or scheduling (integer counts).  Inputs are assumed finite; D < 2^24
+ * (CMHSE_ERR_UNSUPPORTED otherwise).
+ * cmhse_group_rank_exact_workspace(B, Nc, Ns): cmhse_group_rank_workspace(B) plus O(B + Nc + Ns) vectors,
+ * 256-byte aligned; 0 for B <= 0, Nc < B or Ns < B.  Errors, before anything is launched: CMHSE_ERR_ARG as
+ * cmhse_group_rank's (a group of more than 128 rows is cmhse_group_plan's CMHSE_ERR_UNSUPPORTED), then
+ * CMHSE_ERR_WORKSPACE for a workspace that is unaligned (256 bytes) or too small.
+ * Cost: cmhse_group_rank's, one wave per clip / caption row in front (norms), one wave per group (G64[i, i]),
+ * two small launches, and one block64 per undecided block.
+ *
+ * cmhse_group_rank_exact_tolerance(D, reduce, A_i, Bmax): the tolerance as the kernel computes it (before the
+ * tunable's factor and the rounding up to fp32); host-only, no GPU.  NaN for D <= 0, a bad reduce or a negative
+ * norm, +inf for D >= 2^24. */
+size_t cmhse_group_rank_exact_workspace(int32_t B, int32_t Nc, int32_t Ns);
+double cmhse_group_rank_exact_tolerance(int32_t D, int32_t reduce, double norm_a, double norm_b_max);
+int cmhse_group_rank_exact(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                           int32_t B, const int32_t* plan_host, const int32_t* plan, int32_t plan_len,
+                           int32_t reduce, int32_t* rank_lo_v2p, int32_t* rank_hi_v2p, int32_t* top1_v2p,
+                           int32_t* resolved_v2p, int32_t* rank_lo_p2v, int32_t* rank_hi_p2v, int32_t* top1_p2v,
+                           int32_t* resolved_p2v, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Group-wise top-K retrieval: the K best gallery groups of every query group by the block score
  * above, for any video set and any paragraph set (Bv videos of clips, Bp paragraphs of caps: Bv and
  * Bp independent, every count 1..CMHSE_GROUP_TILE_ROWS rows).
