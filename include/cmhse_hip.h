@@ -17,6 +17,10 @@
  *     returns.  Host-side objects a call may take and give back before it returns: HIP events for
  *     stream fork / join (`tail_stream`, `stream`, `side_stream` of the job structs) and the event
  *     pairs owned by a cmhse_timer handle when the caller passes one (measurement only);
+ *   - workspaces and outputs may hold anything on entry and no result depends on what they held
+ *     (an arena reused across calls of other shapes is fine), except the three accumulation targets
+ *     whose comment says "zero it first": cmhse_rows_differ's flag, d_emb_table and the dx row of a
+ *     time-constant input (tests/test_gpu_dirty_workspace.py);
  *   - process-wide state, all of it host-side and mutex- or atomic-guarded: (o) 64 bytes of pinned
  *     host memory per device for cmhse_async_status, allocated at the first resident launch;
  *     (i) per-device free

@@ -51,6 +51,13 @@ Mutants:
   topk_exact_tol_zero, topk_exact_tol_small, topk_exact_tie_larger_column
                  the second pass of the certified top-K (killed by tests/test_gpu_topk_exact.py:
                  profiles/topk_exact_mutation_check.txt)
+  ws_rank_not_zeroed, ws_top1key_not_zeroed, ws_labelled_keys_half_zeroed, ws_exact_pre_keeps_resolved,
+  ws_exact_norm_max_not_zeroed, ws_topk_exact_norm_max_not_zeroed, ws_group_norm_max_not_zeroed, ws_bwd_carry_not_zeroed,
+  ws_bwd_dpool_not_zeroed, ws_bwd_zero_row_not_zeroed, ws_split_k_not_zeroed, ws_bf3_hs_pad_not_zeroed
+                 one deleted or narrowed initialisation of a workspace region or of an output that is counted or
+                 summed into (killed by tests/test_gpu_dirty_workspace.py: profiles/dirty_workspace_mutation_check.txt).
+                 None touches a sync word, a ticket, a barrier counter, the abort word or an address table.  Two change
+                 no result (EQUIVALENT): the carry memset is redundant, the own_zero arm of launch_nt_out has no caller.
 """
 import os
 import shutil
@@ -231,11 +238,51 @@ MUTANTS = {
     # equal float64 scores put the LARGER column first
     'topk_exact_tie_larger_column': ('topk_lists.hpp', 'return xb > yb || (xb == yb && xi < yi);',
                                      'return xb > yb || (xb == yb && xi > yi);'),
+    # dirty workspaces and outputs (tests/test_gpu_dirty_workspace.py): ONE initialisation deleted or narrowed each; wrong
+    # numbers only (counters, keys, sums and norms: no sync word, no address table).
+    # cmhse_sim_rank counts into whatever `rank` held
+    'ws_rank_not_zeroed': ('sim.hip', 'if (hipMemsetAsync(rank, 0, sizeof(int32_t) * nrows, stream) != hipSuccess) return CMHSE_ERR_LAUNCH;\n'
+                           '  if (hipMemsetAsync(p.top1key, 0, sizeof(score_key_t) * nrows, stream) != hipSuccess)',
+                           'if (hipMemsetAsync(p.top1key, 0, sizeof(score_key_t) * nrows, stream) != hipSuccess)'),
+    # ... and takes its top-1 maximum over whatever the key vector held
+    'ws_top1key_not_zeroed': ('sim.hip', 'if (hipMemsetAsync(p.top1key, 0, sizeof(score_key_t) * nrows, stream) != hipSuccess)\n'
+                              '    return CMHSE_ERR_LAUNCH;', ''),
+    # cmhse_sim_rank_labelled clears the top-1 keys and leaves the threshold keys behind them
+    'ws_labelled_keys_half_zeroed': ('sim.hip', 'if (hipMemsetAsync(p.top1key, 0, 2 * sizeof(score_key_t) * nrows, stream) != hipSuccess)',
+                                     'if (hipMemsetAsync(p.top1key, 0, sizeof(score_key_t) * nrows, stream) != hipSuccess)'),
+    # exact_pre_kernel leaves the diagnostic counter of cmhse_sim_rank_exact as it found it
+    'ws_exact_pre_keeps_resolved': ('sim.hip', '      p.s64_diag[r] = sii;\n      p.norm_a[r] = na;\n      p.rank_lo[r] = 0;\n      p.ties[r] = 0;\n'
+                                    '      p.resolved[r] = 0;',
+                                    '      p.s64_diag[r] = sii;\n      p.norm_a[r] = na;\n      p.rank_lo[r] = 0;\n      p.ties[r] = 0;'),
+    # the largest gallery norm of the three certified calls starts from what the word held (atomicMax on the bits)
+    'ws_exact_norm_max_not_zeroed': ('sim.hip', 'if (hipMemsetAsync(q.norm_b_max, 0, sizeof(unsigned), stream) != hipSuccess) return CMHSE_ERR_LAUNCH;\n'
+                                     '  const int64_t pre_rows = static_cast<int64_t>(nrows) + M;\n  hipLaunchKernelGGL(exact_pre_kernel,',
+                                     'const int64_t pre_rows = static_cast<int64_t>(nrows) + M;\n  hipLaunchKernelGGL(exact_pre_kernel,'),
+    'ws_topk_exact_norm_max_not_zeroed': ('topk.hip', 'if (hipMemsetAsync(q.norm_b_max, 0, sizeof(unsigned), stream) != hipSuccess) return CMHSE_ERR_LAUNCH;', ''),
+    'ws_group_norm_max_not_zeroed': ('group.hip', 'if (hipMemsetAsync(q.norm_max, 0, 2 * sizeof(unsigned), stream) != hipSuccess) return CMHSE_ERR_LAUNCH;', ''),
+    # the BPTT's carried dh z starts from what the workspace held (EQUIVALENT: every row is written before it is read)
+    'ws_bwd_carry_not_zeroed': ('bwd.hip', '(void)hipMemsetAsync(carry, 0, static_cast<size_t>(S) * H * 4, st);', ''),
+    # last-state / max pooling scatter their output gradient into rows that were never cleared
+    'ws_bwd_dpool_not_zeroed': ('bwd.hip', '(void)hipMemsetAsync(dpool, 0, static_cast<size_t>(sum_T) * H * 4, st);', '(void)0;'),
+    # the row of zeros that stands in for h_{-1} and for padding keeps its old bytes (the barrier counter behind it is still cleared)
+    'ws_bwd_zero_row_not_zeroed': ('bwd.hip', '(void)hipMemsetAsync(zero_row, 0, L.tail_sync + 256 - L.zero_row, st);',
+                                   '(void)hipMemsetAsync(ws + L.tail_sync, 0, 256, st);'),
+    # launch_nt_out's own_zero arm (split == 1) sums into an uncleared C: no caller passes split == 1
+    'ws_split_k_not_zeroed': ('bwd.hip', 'if (own_zero) (void)hipMemsetAsync(c, 0, static_cast<size_t>(M) * N * sizeof(float), st);', ''),
+    # bf16x3, H % 16 != 0: the chunk padding of the pre-split hidden states keeps its old bytes
+    'ws_bf3_hs_pad_not_zeroed': ('gru.hip', 'if (b->H % 16 != 0)   // the epilogue writes whole (hi, lo) pairs; the chunk padding must read 0\n'
+                                 '        (void)hipMemsetAsync(wsb + L.hs_s, 0,\n'
+                                 '                             static_cast<size_t>(job->rows_split) * split_ld(b->H) * sizeof(float), stream);', ''),
 }
 # mutants that change no result, with the reason: run and reported, but no test can kill them
 EQUIVALENT = {
     'bf3_tiled_wgs_counts_bf3': 'moves an exact request between 64- and 128-row tiles, which give the same bits; the line is '
                                 'pinned by tests/test_bf3_shapes_cpu.py (fwd_shapes.TILED_WGS_ALSO)',
+    'ws_bwd_carry_not_zeroed': 'every BPTT step kernel reads carry only at rows m < S_next, which the step before it wrote '
+                               '(bwd_step_kernels.hpp; the last step has S_next = 0, the resident tail starts from a register): '
+                               'the memset in bwd_begin is belt and braces and no result can show that it is gone',
+    'ws_split_k_not_zeroed': 'the own_zero arm of launch_nt_out has no caller (tests/test_bwd_side_shapes_cpu.py '
+                             'test_the_own_zero_arm_has_no_caller): the deleted memset cannot run',
 }
 # the tests that must kill them (and pass on the product library)
 SELECT = ['tests/test_quirks_tight.py', 'tests/test_gpu_golden.py', 'tests/test_gpu_gru.py', 'tests/test_gpu_scoring.py',
