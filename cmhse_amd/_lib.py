@@ -154,6 +154,12 @@ SIGNATURES = {
     'cmhse_group_topk': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                         c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),
+    'cmhse_group_topk_exact_plan': (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                              c_int32]),
+    'cmhse_group_topk_exact_workspace': (c_size_t, [c_void_p, c_int32]),
+    'cmhse_group_topk_exact': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                              c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_size_t, c_void_p]),
     'cmhse_cosine_sim': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                         c_void_p]),
     'cmhse_contrastive_workspace': (c_size_t, [c_int32]),

@@ -36,6 +36,15 @@
 //                             against each query's K-th key, wave_merge (topk_lists.hpp) into its
 //                             sorted list in LDS, the panel's lists to the workspace at the end;
 //   group_topk_merge_kernel   merge_panel_lists (topk_lists.hpp): the panels' lists of each query.
+//
+// Certified group-wise top-K (cmhse_group_topk_exact: the K best gallery groups by the float64 block scores):
+//   cmhse_group_topk itself   into a private region of the workspace: G_K(q), the K-th fp32 block score;
+//   group_topk_exact_pre_kernel / group_topk_exact_tol_kernel   the query rows' norms, the largest norm of
+//                             each side, a tolerance per query group;
+//   group_topk_exact_select_kernel   group_topk_select_kernel's grid, tile loop and block reduction; every
+//                             gallery group that G_K cannot rule out goes through block64 and into the query's
+//                             list of K (float64 bits, index) pairs in LDS (wave_merge_pairs);
+//   group_topk_exact_merge_kernel    merge_panel_pair_lists: the panels' lists and counts of each query.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -309,6 +318,205 @@ __global__ __launch_bounds__(kThreads) void group_topk_merge_kernel(const PanelL
   const int li = blockIdx.x * (kThreads / 64) + wave;
   if (li >= p.nrows) return;   // (no barrier below)
   merge_panel_lists(p, li, s_list[wave], s_cand[wave], lane);
+}
+
+// ---- certified group-wise top-K (cmhse_group_topk_exact) -------------------------------------------
+// The K best gallery groups of every query group by the FLOAT64 block scores G64 (exact64.hpp: block64, the one
+// routine cmhse_group_rank_exact takes its scores from), certified.  cmhse_group_topk gives the K-th fp32 block
+// score G_K(q) of every query; a second pass of the same grid, group_topk_exact_select_kernel, takes every
+// gallery group with fl(G_K(q) - G32(q,g)) <= tol_q through block64 and keeps the K best (float64 bits, gallery
+// index) pairs per query in LDS; group_topk_exact_merge_kernel merges the panels.
+// Why the candidates hold the whole float64 top-K: topk.hip's argument with group_exact_tolerance (exact64.hpp)
+// in the place of exact_tolerance.  E_q bounds |G32(q,g) - G64(q,g)| for every gallery group g: the row-wise
+// statement of exact64.hpp for a video query (A_q = the largest clip norm of video q, Bmax = the largest caption
+// norm of the call), the column-wise one for a paragraph query (B_q and Amax); under 'mean' E_q carries the two
+// float64 summations and the rounding of G32 to fp32, terms (2) and (3) there, which bound |G32 - G64| of ONE
+// block and so serve a threshold G_K taken from another block of the same line as they serve the diagonal.
+// tol_q = 2 E_q (1 + 2^-18).  The K groups of the fp32 list have G32 >= G_K, hence G64 >= G_K - E_q: the K-th
+// largest G64 of the query is at least G_K - E_q.  A member g of the float64 top-K has G64(q,g) at least that
+// (on a tie at the boundary too: the index decides among equals, the score bound is the same), so
+// G32(q,g) >= G64(q,g) - E_q >= G_K - 2 E_q; the factor on tol_q covers the rounding of fl(G_K - G32).  The
+// block scores of the second pass come out of the same nt_phase call and the same group_tile_reduce as the
+// first's, bit for bit, so the fp32 list's own K groups always qualify (G_K - G32 <= 0) and every list fills.
+// The exact top-K of a superset of the top-K is the top-K.
+//
+// LDS of a workgroup: the 40 KB tile buffers, one 128-pair candidate buffer per wave, then per query group its
+// list (K pairs of 12 bytes), its row of block scores and three words (candidate count, G_K, tolerance):
+// [tile][candidate bits 4 x 128][list bits nQ x K][candidate index 4 x 128][list index nQ x K][blk nQ x 129]
+// [count nQ][G_K nQ][tol nQ] — the 64-bit arrays first.
+constexpr size_t kGteFixed = kGrSmem + (sizeof(score_bits64_t) + sizeof(int32_t)) * kGtGalleryMax * (kThreads / 64);
+constexpr size_t kGteRowWords = 3;
+
+struct GroupTopkExactParams {
+  GroupTopkParams t;        // the inputs, the plan and the grid (panels: this pass's own; ws unused)
+  const float* g32;         // [Bq, K] the fp32 lists' scores: column K - 1 is G_K
+  const float* tol;         // [Bq]
+  score_bits64_t* ws_bits;  // [panels, Bq, K] sorted pairs of each panel
+  int32_t* ws_idx;          // [panels, Bq, K]
+  int32_t* ws_count;        // [panels, Bq] candidates of each panel
+};
+
+struct GroupTopkExactPreParams {
+  const float* C;           // [Nc, D] clip rows
+  const float* S;           // [Ns, D] caption rows
+  int32_t D, Nc, Ns, p2v, Bq, use_max, scale;
+  const int32_t* q_off;     // [Bq + 1] the query side's offsets (device copy of the plan)
+  double* norm_q;           // [query rows]
+  unsigned* norm_max;       // [0]: bits of the largest clip norm, [1]: of the largest caption norm (zeroed)
+  float* tol;               // [Bq]
+};
+
+// group_exact_pre_kernel for two independent sets: one wave per clip / caption row, the largest norm of each
+// side (rounded up to fp32, atomic max on the bits), and the norms of the QUERY side's rows stored (the
+// gallery's are needed through their maximum only: the workspace does not grow with the gallery).
+__global__ __launch_bounds__(kThreads) void group_topk_exact_pre_kernel(const GroupTopkExactPreParams p) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6);
+  if (r >= static_cast<int64_t>(p.Nc) + p.Ns) return;   // (wave-uniform)
+  const bool cap = r >= p.Nc;
+  const int64_t row = cap ? r - p.Nc : r;
+  const float* x = (cap ? p.S : p.C) + row * p.D;
+  const float* const xs[1] = {x};
+  double xx[1];
+  dot64_wide<1, 8>(x, xs, p.D, lane, xx);   // (dot64(x, x)'s bits, eight loads in flight)
+  const double n = sqrt(xx[0]);
+  if (lane == 0) {
+    if (cap == (p.p2v != 0)) p.norm_q[row] = n;
+    atomicMax(p.norm_max + (cap ? 1 : 0), __float_as_uint(round_up_f32(n)));
+  }
+}
+
+// thread q < Bq: the query group's largest norm against the largest norm of the gallery side
+__global__ void group_topk_exact_tol_kernel(const GroupTopkExactPreParams p) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= p.Bq) return;
+  double mine = 0.0;
+  for (int r = p.q_off[q]; r < p.q_off[q + 1]; ++r) mine = p.norm_q[r] > mine ? p.norm_q[r] : mine;
+  const double other = static_cast<double>(__uint_as_float(p.norm_max[p.p2v ? 0 : 1]));
+  p.tol[q] = round_up_f32(group_exact_tolerance(p.D, p.use_max != 0, mine, other) * static_cast<double>(p.scale));
+}
+
+// group_topk_select_kernel's walk, tile loop and block reduction (the fp32 block scores in blk are pass one's,
+// bit for bit); per query group, the gallery groups that G_K cannot rule out get their block64 — all of them,
+// so the count is a function of the inputs — and their pairs are merged into the query's list.  block64 keeps
+// its clip-major orientation whichever side is the query.  Loops are bounded by the tile's 128 gallery groups
+// and a block's 128 x 128 rows; nothing waits on another workgroup.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void group_topk_exact_select_kernel(const GroupTopkExactParams pp) {
+  const GroupTopkParams& p = pp.t;
+  // (group_topk_select_kernel's walk of the panel-major work list, as topk_lists.hpp restates it)
+  const PanelWork w = panel_work(blockIdx.x, gridDim.x, p.q_tiles, p.g_tiles, p.panels);
+  if (w.panel < 0) return;   // padding of the grid to a multiple of 8
+  const int panel = w.panel, qt = w.row_tile;
+  const int t_begin = w.t_begin, t_end = w.t_end;
+  const int K = p.K;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, srow = tid >> 2;
+  const int32_t* q_start = p.p2v ? p.ct_par : p.rt_vid;
+  const int32_t* g_start = p.p2v ? p.rt_vid : p.ct_par;
+  const int qg0 = q_start[qt], nQ = q_start[qt + 1] - qg0;   // nQ <= gte_qcap(K): the plan is checked
+
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  char* lds = reinterpret_cast<char*>(smem);
+  score_bits64_t* cbits_all = reinterpret_cast<score_bits64_t*>(lds + kGrSmem);          // [waves][128]
+  score_bits64_t* lbits = cbits_all + kGtGalleryMax * (kThreads / 64);                   // [nQ][K]
+  int32_t* cidx_all = reinterpret_cast<int32_t*>(lbits + nQ * K);                        // [waves][128]
+  int32_t* lidx = cidx_all + kGtGalleryMax * (kThreads / 64);                            // [nQ][K]
+  float* blk = reinterpret_cast<float*>(lidx + nQ * K);                                  // [nQ][kGtBlkLd]
+  int32_t* s_count = reinterpret_cast<int32_t*>(blk + nQ * kGtBlkLd);                    // [nQ]
+  float* s_gk = reinterpret_cast<float*>(s_count + nQ);                                  // [nQ]
+  float* s_tol = s_gk + nQ;                                                              // [nQ]
+  score_bits64_t* cbits = cbits_all + wave * kGtGalleryMax;
+  int32_t* cidx = cidx_all + wave * kGtGalleryMax;
+  // (all seen after nt_phase's barriers; every panel has a tile: panels <= g_tiles)
+  for (int e = tid; e < nQ * K; e += kThreads) {
+    lbits[e] = 0ull;
+    lidx[e] = kNoColumn;
+  }
+  if (tid < nQ) {
+    s_count[tid] = 0;
+    s_gk[tid] = pp.g32[static_cast<int64_t>(qg0 + tid) * K + (K - 1)];
+    s_tol[tid] = pp.tol[qg0 + tid];
+  }
+  const bool use_max = p.use_max != 0;
+
+  const int b_row0[2] = {wn * 64, wn * 64 + 32};
+  for (int t = t_begin; t < t_end; ++t) {
+    const int gg0 = g_start[t], nG = g_start[t + 1] - gg0;
+    const int v0 = p.p2v ? gg0 : qg0, nv = p.p2v ? nG : nQ;
+    const int q0 = p.p2v ? qg0 : gg0, nq = p.p2v ? nQ : nG;
+    const int r_begin = p.clip_off[v0], nr = p.clip_off[v0 + nv] - r_begin;
+    const int c_begin = p.cap_off[q0], nc = p.cap_off[q0 + nq] - c_begin;
+    const int my_voff = (tid <= nv) ? p.clip_off[v0 + tid] - r_begin : 0;
+    const int my_poff = (tid <= nq) ? p.cap_off[q0 + tid] - c_begin : 0;
+    rowaddr_t ar[kGrBM / 64], br[kGrBN / 64];
+    bool av[kGrBM / 64], bv[kGrBN / 64];
+#pragma unroll
+    for (int i = 0; i < kGrBM / 64; ++i) ar[i] = tile_row(p.C, p.D, r_begin, srow + 64 * i, nr, &av[i]);
+#pragma unroll
+    for (int i = 0; i < kGrBN / 64; ++i) br[i] = tile_row(p.S, p.D, c_begin, srow + 64 * i, nc, &bv[i]);
+    f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
+    // ends with a barrier: every wave is done with the tile buffers (and with the previous tile's
+    // selection, so blk is free)
+    nt_phase<kGrBM, kGrBN, 2, 2, 2, 1, VEC>(smem, ar, av, br, bv, p.D, wm * 64, b_row0, acc);
+    const bool p2v = p.p2v;
+    group_tile_reduce(smem, acc, nv, nq, nr, my_voff, my_poff, p.use_max, [&](int v, int q, float g) {
+      blk[p2v ? q * kGtBlkLd + v : v * kGtBlkLd + q] = g;
+    });
+    // (the wave index in a scalar register: the candidates' offsets and block64's loop bounds stay scalar)
+    for (int qi = __builtin_amdgcn_readfirstlane(wave); qi < nQ; qi += kThreads / 64) {
+      const float* row = blk + qi * kGtBlkLd;
+      const float gk = s_gk[qi];
+      const float tol = s_tol[qi];
+      // not ruled out: NOT (fl(G_K - G32) > tol); tol >= 0, possibly +inf (every group); inputs finite, so the
+      // difference is no NaN.  Slots past nG hold the previous tile's scores and are never candidates.
+      const bool c0 = lane < nG && !(gk - row[lane] > tol);
+      const bool c1 = lane + 64 < nG && !(gk - row[lane + 64] > tol);
+      const unsigned long long m[2] = {__ballot(c0), __ballot(c1)};   // (wave-uniform, scalar registers)
+      if ((m[0] | m[1]) == 0ull) continue;
+      const int qg = qg0 + qi;
+      // the query's own rows: its clips (v2p) or its captions (p2v); the candidate gives the other side
+      const int own0 = p2v ? p.cap_off[qg] : p.clip_off[qg], own1 = p2v ? p.cap_off[qg + 1] : p.clip_off[qg + 1];
+      int c = 0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        unsigned long long bits = m[h];
+        while (bits != 0ull) {
+          const int g = gg0 + 64 * h + (__ffsll(static_cast<long long>(bits)) - 1);
+          bits &= bits - 1ull;
+          const double s = p2v ? block64(p.C, p.S, p.D, p.clip_off[g], p.clip_off[g + 1], own0, own1, use_max, lane)
+                               : block64(p.C, p.S, p.D, own0, own1, p.cap_off[g], p.cap_off[g + 1], use_max, lane);
+          if (lane == 0) {
+            cbits[c] = ordered_bits64(s);
+            cidx[c] = g;
+          }
+          ++c;
+        }
+      }
+      if (lane == 0) s_count[qi] += c;
+      __builtin_amdgcn_wave_barrier();
+      wave_merge_pairs(lbits + qi * K, lidx + qi * K, K, cbits, cidx, c, lane);
+    }
+  }
+  __syncthreads();
+  const int64_t out_row = static_cast<int64_t>(panel) * p.Bq + qg0;
+  for (int e = tid; e < nQ * K; e += kThreads) {
+    pp.ws_bits[out_row * K + e] = lbits[e];
+    pp.ws_idx[out_row * K + e] = lidx[e];
+  }
+  if (tid < nQ) pp.ws_count[out_row + tid] = s_count[tid];
+}
+
+// One wave per query: the P panel lists into one, decoded to float64, and the panels' counts summed.
+__global__ __launch_bounds__(kThreads) void group_topk_exact_merge_kernel(const PanelPairLists p) {
+  __shared__ score_bits64_t s_lb[kThreads / 64][CMHSE_TOPK_MAX];
+  __shared__ score_bits64_t s_cb[kThreads / 64][CMHSE_TOPK_MAX];
+  __shared__ int32_t s_li[kThreads / 64][CMHSE_TOPK_MAX];
+  __shared__ int32_t s_ci[kThreads / 64][CMHSE_TOPK_MAX];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = blockIdx.x * (kThreads / 64) + wave;
+  if (li >= p.nrows) return;   // (no barrier below)
+  merge_panel_pair_lists(p, li, s_lb[wave], s_li[wave], s_cb[wave], s_ci[wave], lane);
 }
 
 struct GroupRankParams {
@@ -713,8 +921,8 @@ size_t gt_smem(int32_t K) {
 // (~140 query tiles) P0 is 1 at K = 128 (256 slots: over 100 CUs idle) and 3 at K = 50 (512 slots,
 // ~420 busy); P = 7 runs both in nearly whole rounds.  The count depends on the query tiles and K
 // only — it does not grow with the gallery, nor does the workspace.
-int32_t gt_panels(int32_t q_tiles, int32_t g_tiles, int32_t K) {
-  int per_cu = static_cast<int>(kGtLdsPerCU / gt_smem(K));
+int32_t gt_panels_for_smem(int32_t q_tiles, int32_t g_tiles, size_t smem) {
+  int per_cu = static_cast<int>(kGtLdsPerCU / smem);
   per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
   const int64_t slots = static_cast<int64_t>(kGtCUs) * per_cu;
   const int64_t P0 = slots / q_tiles < 1 ? 1 : slots / q_tiles;
@@ -727,6 +935,10 @@ int32_t gt_panels(int32_t q_tiles, int32_t g_tiles, int32_t K) {
     }
   }
   return static_cast<int32_t>(best < g_tiles ? best : g_tiles);
+}
+
+int32_t gt_panels(int32_t q_tiles, int32_t g_tiles, int32_t K) {
+  return gt_panels_for_smem(q_tiles, g_tiles, gt_smem(K));
 }
 
 int64_t gt_plan_len(int64_t Bv, int64_t Bp, int64_t R, int64_t Cc) { return kGtHdr + Bv + Bp + R + Cc + 4; }
@@ -751,6 +963,74 @@ bool gt_plan_ok(const int32_t* ph, int32_t len, int32_t Nc, int32_t Ns, int32_t 
          tiles_ok(ctp, Cc, cap_off, Bp, kGrBN, direction == CMHSE_GROUP_P2V ? qcap : 0x7fffffff);
 }
 
+
+// ---- cmhse_group_topk_exact: its query-group cap, LDS, panels and plan check ----
+// Query groups per query tile of the certified pass: gt_qcap's rule with this kernel's LDS (12-byte list
+// entries, the pair candidate buffers, three words a group) — two workgroups per CU where that leaves at least
+// 32 groups, else one — and never above gt_qcap(K), so a plan packed to this cap is valid for the nested fp32
+// call too.  K = 1 / 10 / 50 / 128: 64 / 48 / 40 / 56 query groups, 80 / 76 / 90 / 159 KB of LDS, 2 / 2 / 1 / 1
+// workgroups per CU (at K = 50 the rule's 64 is cut to gt_qcap's 40).
+constexpr size_t gte_per_q(int32_t K) {
+  return (sizeof(score_bits64_t) + sizeof(int32_t)) * K + sizeof(float) * kGtBlkLd + sizeof(int32_t) * kGteRowWords;
+}
+
+int32_t gte_qcap(int32_t K) {
+  const size_t per_q = gte_per_q(K);
+  int32_t q = static_cast<int32_t>((kGtLdsPerCU / 2 - kGteFixed) / per_q) / 8 * 8;
+  if (q < 32) q = static_cast<int32_t>((kGtLdsPerCU - kGteFixed) / per_q) / 8 * 8;
+  const int32_t q32 = gt_qcap(K);
+  return q > q32 ? q32 : q;
+}
+
+size_t gte_smem(int32_t K) { return kGteFixed + gte_per_q(K) * static_cast<size_t>(gte_qcap(K)); }
+
+int32_t gte_panels(int32_t q_tiles, int32_t g_tiles, int32_t K) {
+  return gt_panels_for_smem(q_tiles, g_tiles, gte_smem(K));
+}
+
+// gt_plan_ok, and the query tiles within this pass's cap (a plan of cmhse_group_topk_plan can exceed it)
+bool gte_plan_ok(const int32_t* ph, int32_t len, int32_t Nc, int32_t Ns, int32_t direction, int32_t K) {
+  if (!gt_plan_ok(ph, len, Nc, Ns, direction, K)) return false;
+  const int32_t Bv = ph[0], Bp = ph[1], R = ph[6], Cc = ph[7];
+  const int32_t* rt = ph + kGtHdr + Bv + 1 + Bp + 1;
+  const int32_t* start = direction == CMHSE_GROUP_P2V ? rt + R + 1 : rt;
+  const int32_t T = direction == CMHSE_GROUP_P2V ? Cc : R, qcap = gte_qcap(K);
+  for (int32_t t = 0; t < T; ++t)
+    if (start[t + 1] - start[t] > qcap) return false;
+  return true;
+}
+
+// cmhse_group_topk_plan and cmhse_group_topk_exact_plan: one layout, the query side capped at qcap groups a tile
+int32_t gt_plan_fill(const int32_t* clip_off_host, int32_t Bv, const int32_t* cap_off_host, int32_t Bp,
+                     int32_t direction, int32_t K, int32_t* plan, int32_t plan_cap, int32_t (*qcap_of)(int32_t)) {
+  if (!clip_off_host || !cap_off_host || !plan || Bv <= 0 || Bp <= 0) return CMHSE_ERR_ARG;
+  if (direction != CMHSE_GROUP_P2V && direction != CMHSE_GROUP_V2P) return CMHSE_ERR_ARG;
+  const int32_t Bg = direction == CMHSE_GROUP_P2V ? Bv : Bp;
+  if (K < 1 || K > CMHSE_TOPK_MAX || K > Bg) return CMHSE_ERR_ARG;
+  if (!offsets_ok(clip_off_host, Bv) || !offsets_ok(cap_off_host, Bp)) return CMHSE_ERR_ARG;
+  for (int32_t b = 0; b < Bv; ++b)
+    if (clip_off_host[b + 1] - clip_off_host[b] > kGrBM) return CMHSE_ERR_UNSUPPORTED;
+  for (int32_t b = 0; b < Bp; ++b)
+    if (cap_off_host[b + 1] - cap_off_host[b] > kGrBN) return CMHSE_ERR_UNSUPPORTED;
+  if (plan_cap < gt_plan_len(Bv, Bp, Bv, Bp)) return CMHSE_ERR_WORKSPACE;   // CMHSE_GROUP_TOPK_PLAN_MAX
+  plan[0] = Bv;
+  plan[1] = Bp;
+  plan[2] = clip_off_host[Bv];
+  plan[3] = cap_off_host[Bp];
+  plan[4] = direction;
+  plan[5] = K;
+  int32_t* clip_off = plan + kGtHdr;
+  int32_t* cap_off = clip_off + Bv + 1;
+  for (int32_t b = 0; b <= Bv; ++b) clip_off[b] = clip_off_host[b];
+  for (int32_t b = 0; b <= Bp; ++b) cap_off[b] = cap_off_host[b];
+  const int32_t qcap = qcap_of(K);
+  int32_t* rt = cap_off + Bp + 1;
+  const int32_t R = pack(clip_off, Bv, kGrBM, rt, direction == CMHSE_GROUP_V2P ? qcap : 0x7fffffff);
+  const int32_t Cc = pack(cap_off, Bp, kGrBN, rt + R + 1, direction == CMHSE_GROUP_P2V ? qcap : 0x7fffffff);
+  plan[6] = R;
+  plan[7] = Cc;
+  return static_cast<int32_t>(gt_plan_len(Bv, Bp, R, Cc));
+}
 
 bool group_args_ok(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D, int32_t B,
                    const int32_t* plan_host, const int32_t* plan, int32_t plan_len_, int32_t reduce) {
@@ -973,33 +1253,7 @@ extern "C" int cmhse_group_rank_exact(const float* clips, const float* caps, int
 
 extern "C" int32_t cmhse_group_topk_plan(const int32_t* clip_off_host, int32_t Bv, const int32_t* cap_off_host,
                                          int32_t Bp, int32_t direction, int32_t K, int32_t* plan, int32_t plan_cap) {
-  if (!clip_off_host || !cap_off_host || !plan || Bv <= 0 || Bp <= 0) return CMHSE_ERR_ARG;
-  if (direction != CMHSE_GROUP_P2V && direction != CMHSE_GROUP_V2P) return CMHSE_ERR_ARG;
-  const int32_t Bg = direction == CMHSE_GROUP_P2V ? Bv : Bp;
-  if (K < 1 || K > CMHSE_TOPK_MAX || K > Bg) return CMHSE_ERR_ARG;
-  if (!offsets_ok(clip_off_host, Bv) || !offsets_ok(cap_off_host, Bp)) return CMHSE_ERR_ARG;
-  for (int32_t b = 0; b < Bv; ++b)
-    if (clip_off_host[b + 1] - clip_off_host[b] > kGrBM) return CMHSE_ERR_UNSUPPORTED;
-  for (int32_t b = 0; b < Bp; ++b)
-    if (cap_off_host[b + 1] - cap_off_host[b] > kGrBN) return CMHSE_ERR_UNSUPPORTED;
-  if (plan_cap < gt_plan_len(Bv, Bp, Bv, Bp)) return CMHSE_ERR_WORKSPACE;   // CMHSE_GROUP_TOPK_PLAN_MAX
-  plan[0] = Bv;
-  plan[1] = Bp;
-  plan[2] = clip_off_host[Bv];
-  plan[3] = cap_off_host[Bp];
-  plan[4] = direction;
-  plan[5] = K;
-  int32_t* clip_off = plan + kGtHdr;
-  int32_t* cap_off = clip_off + Bv + 1;
-  for (int32_t b = 0; b <= Bv; ++b) clip_off[b] = clip_off_host[b];
-  for (int32_t b = 0; b <= Bp; ++b) cap_off[b] = cap_off_host[b];
-  const int32_t qcap = gt_qcap(K);
-  int32_t* rt = cap_off + Bp + 1;
-  const int32_t R = pack(clip_off, Bv, kGrBM, rt, direction == CMHSE_GROUP_V2P ? qcap : 0x7fffffff);
-  const int32_t Cc = pack(cap_off, Bp, kGrBN, rt + R + 1, direction == CMHSE_GROUP_P2V ? qcap : 0x7fffffff);
-  plan[6] = R;
-  plan[7] = Cc;
-  return static_cast<int32_t>(gt_plan_len(Bv, Bp, R, Cc));
+  return gt_plan_fill(clip_off_host, Bv, cap_off_host, Bp, direction, K, plan, plan_cap, gt_qcap);
 }
 
 extern "C" size_t cmhse_group_topk_workspace(const int32_t* plan_host, int32_t plan_len_) {
@@ -1049,5 +1303,127 @@ extern "C" int cmhse_group_topk(const float* clips, const float* caps, int32_t N
   if (rc != CMHSE_OK) return rc;
   const PanelLists lists = {p.ws, p.panels, p.Bq, K, scores, index};
   hipLaunchKernelGGL(group_topk_merge_kernel, dim3((p.Bq + 3) / 4), dim3(kThreads), 0, stream, lists);
+  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
+}
+
+extern "C" int32_t cmhse_group_topk_exact_plan(const int32_t* clip_off_host, int32_t Bv, const int32_t* cap_off_host,
+                                               int32_t Bp, int32_t direction, int32_t K, int32_t* plan,
+                                               int32_t plan_cap) {
+  return gt_plan_fill(clip_off_host, Bv, cap_off_host, Bp, direction, K, plan, plan_cap, gte_qcap);
+}
+
+namespace {
+// cmhse_group_topk's workspace (its panel keys) and its two outputs (the fp32 lists), the query rows' norms, the
+// tolerances, the two largest norms, and one list of K pairs and one count per query group and panel.
+struct GroupTopkExactWs {
+  size_t keys32, scores32, index32, norm_q, tol, norm_max, bits, idx, count, total;
+  int32_t panels;
+};
+
+// (plan_host: gte_plan_ok has passed)
+GroupTopkExactWs group_topk_exact_ws(const int32_t* plan_host, int32_t plan_len_) {
+  const bool p2v = plan_host[4] == CMHSE_GROUP_P2V;
+  const int32_t K = plan_host[5];
+  const size_t Bq = static_cast<size_t>(p2v ? plan_host[1] : plan_host[0]), nk = Bq * static_cast<size_t>(K);
+  const size_t q_rows = static_cast<size_t>(p2v ? plan_host[3] : plan_host[2]);
+  const int32_t q_tiles = p2v ? plan_host[7] : plan_host[6], g_tiles = p2v ? plan_host[6] : plan_host[7];
+  GroupTopkExactWs L;
+  L.panels = gte_panels(q_tiles, g_tiles, K);
+  const size_t P = static_cast<size_t>(L.panels);
+  size_t off = 0;
+  L.keys32 = off, off += cmhse_group_topk_workspace(plan_host, plan_len_);
+  L.scores32 = off, off += align256(nk * sizeof(float));
+  L.index32 = off, off += align256(nk * sizeof(int32_t));
+  L.norm_q = off, off += align256(q_rows * sizeof(double));
+  L.tol = off, off += align256(Bq * sizeof(float));
+  L.norm_max = off, off += 256;
+  L.bits = off, off += align256(P * nk * sizeof(score_bits64_t));
+  L.idx = off, off += align256(P * nk * sizeof(int32_t));
+  L.count = off, off += align256(P * Bq * sizeof(int32_t));
+  L.total = off;
+  return L;
+}
+}  // namespace
+
+extern "C" size_t cmhse_group_topk_exact_workspace(const int32_t* plan_host, int32_t plan_len_) {
+  if (!plan_host || plan_len_ < kGtHdr ||
+      !gte_plan_ok(plan_host, plan_len_, plan_host[2], plan_host[3], plan_host[4], plan_host[5]))
+    return 0;
+  return group_topk_exact_ws(plan_host, plan_len_).total;
+}
+
+extern "C" int cmhse_group_topk_exact(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                                      const int32_t* plan_host, const int32_t* plan, int32_t plan_len_,
+                                      int32_t direction, int32_t reduce, int32_t K, double* scores, int32_t* index,
+                                      int32_t* resolved, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!clips || !caps || !plan_host || !plan || !scores || !index || !resolved || !workspace) return CMHSE_ERR_ARG;
+  if (Nc <= 0 || Ns <= 0 || D <= 0) return CMHSE_ERR_ARG;
+  if (reduce != CMHSE_GROUP_MAX && reduce != CMHSE_GROUP_MEAN) return CMHSE_ERR_ARG;
+  // (cmhse_group_topk's plan check, and the query tiles within this pass's LDS)
+  if (!gte_plan_ok(plan_host, plan_len_, Nc, Ns, direction, K)) return CMHSE_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
+      workspace_bytes < cmhse_group_topk_exact_workspace(plan_host, plan_len_))
+    return CMHSE_ERR_WORKSPACE;
+  if (D >= (1 << 24)) return CMHSE_ERR_UNSUPPORTED;   // (the bound needs D u < 1)
+  const int32_t Bv = plan_host[0], Bp = plan_host[1], R = plan_host[6], Cc = plan_host[7];
+  const GroupTopkExactWs L = group_topk_exact_ws(plan_host, plan_len_);
+  char* const ws = static_cast<char*>(workspace);
+  GroupTopkExactParams pp;
+  GroupTopkParams& p = pp.t;
+  p.C = clips;
+  p.S = caps;
+  p.D = D;
+  p.use_max = reduce == CMHSE_GROUP_MAX;
+  p.p2v = direction == CMHSE_GROUP_P2V;
+  p.K = K;
+  p.Bq = p.p2v ? Bp : Bv;
+  p.q_tiles = p.p2v ? Cc : R;
+  p.g_tiles = p.p2v ? R : Cc;
+  p.panels = L.panels;
+  p.clip_off = plan + kGtHdr;
+  p.cap_off = p.clip_off + Bv + 1;
+  p.rt_vid = p.cap_off + Bp + 1;
+  p.ct_par = p.rt_vid + R + 1;
+  p.ws = nullptr;
+  pp.g32 = reinterpret_cast<float*>(ws + L.scores32);
+  pp.tol = reinterpret_cast<float*>(ws + L.tol);
+  pp.ws_bits = reinterpret_cast<score_bits64_t*>(ws + L.bits);
+  pp.ws_idx = reinterpret_cast<int32_t*>(ws + L.idx);
+  pp.ws_count = reinterpret_cast<int32_t*>(ws + L.count);
+  constexpr int kWaves = kThreads / 64;
+  const int64_t blocks = panel_grid_blocks(p.q_tiles, p.panels);
+  const int64_t pre_blocks = (static_cast<int64_t>(Nc) + Ns + kWaves - 1) / kWaves;
+  if (blocks > 0x7fffffffLL || pre_blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  // 1. the fp32 lists: G_K (first: the one nested call that checks arguments of its own)
+  int rc = cmhse_group_topk(clips, caps, Nc, Ns, D, plan_host, plan, plan_len_, direction, reduce, K,
+                            reinterpret_cast<float*>(ws + L.scores32), reinterpret_cast<int32_t*>(ws + L.index32),
+                            ws + L.keys32, cmhse_group_topk_workspace(plan_host, plan_len_), stream_);
+  if (rc != CMHSE_OK) return rc;
+  // 2. norms and tolerances
+  GroupTopkExactPreParams q;
+  q.C = clips;
+  q.S = caps;
+  q.D = D;
+  q.Nc = Nc;
+  q.Ns = Ns;
+  q.p2v = p.p2v;
+  q.Bq = p.Bq;
+  q.use_max = p.use_max;
+  q.scale = tunables().rank_exact_tol_scale.load(std::memory_order_relaxed);
+  q.q_off = p.p2v ? p.cap_off : p.clip_off;
+  q.norm_q = reinterpret_cast<double*>(ws + L.norm_q);
+  q.norm_max = reinterpret_cast<unsigned*>(ws + L.norm_max);
+  q.tol = reinterpret_cast<float*>(ws + L.tol);
+  if (hipMemsetAsync(q.norm_max, 0, 2 * sizeof(unsigned), stream) != hipSuccess) return CMHSE_ERR_LAUNCH;
+  hipLaunchKernelGGL(group_topk_exact_pre_kernel, dim3(static_cast<unsigned>(pre_blocks)), dim3(kThreads), 0, stream,
+                     q);
+  hipLaunchKernelGGL(group_topk_exact_tol_kernel, dim3((p.Bq + 255) / 256), dim3(256), 0, stream, q);
+  // 3. the candidates in float64, 4. the panels merged
+  rc = launch_tiles(group_topk_exact_select_kernel<true>, group_topk_exact_select_kernel<false>, D,
+                    dim3(static_cast<unsigned>(blocks)), gte_smem(K), stream, pp);
+  if (rc != CMHSE_OK) return rc;
+  const PanelPairLists lists = {pp.ws_bits, pp.ws_idx, pp.ws_count, p.panels, p.Bq, K, scores, index, resolved};
+  hipLaunchKernelGGL(group_topk_exact_merge_kernel, dim3((p.Bq + 3) / 4), dim3(kThreads), 0, stream, lists);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }

@@ -1087,7 +1087,8 @@ def group_i2t_t2i(clip_embs, cap_embs, num_clips, num_caps=None, reduce='max'):
           (report_from_ranks(host[2]), host[3], host[2]))
 
 
-def group_i2t_t2i_exact(clip_embs, cap_embs, num_clips, num_caps=None, reduce='max', ties='optimistic'):
+def group_i2t_t2i_exact(clip_embs, cap_embs, num_clips, num_caps=None, reduce='max', ties='optimistic',
+                        top1='fp32'):
   """group_i2t_t2i on the ranks of the FLOAT64 block scores, certified (ops.group_rank_exact): independent of
   summation order, tile shape and machine, where the fp32 group ranks differ from a float64 ranking of the
   same rows wherever captions are shared or clips nearly repeat.  Returns ((report, top1, ranks) video ->
@@ -1095,12 +1096,14 @@ def group_i2t_t2i_exact(clip_embs, cap_embs, num_clips, num_caps=None, reduce='m
   for ties='optimistic' (a group that ties the query's own exactly is not counted: group_i2t_t2i's rule) and
   rank_hi for ties='pessimistic' (it is: a model that collapses the low level reports the last rank, not the
   first).  info = {'v2p': d, 'p2v': d, 'resolved': total}, each d with 'report_lo', 'report_hi', 'tied_rows'
-  (the queries with rank_lo < rank_hi) and 'resolved' (the blocks that went through float64).  top1 is
-  group_i2t_t2i's, not certified.  NumPy in: NumPy out (float64) with one device-to-host copy; GPU tensors in:
+  (the queries with rank_lo < rank_hi) and 'resolved' (the blocks that went through float64).  top1='fp32'
+  (the default): top1 is group_i2t_t2i's, not certified; top1='exact': the arg-max of the float64 block
+  scores, the smaller index on a float64 tie, from a certified k = 1 retrieval (ops.group_topk_exact) per
+  direction, whose float64 blocks are counted in info['v2p' / 'p2v']['top1_resolved'] and, summed, in
+  info['top1_resolved'].  NumPy in: NumPy out (float64) with one device-to-host copy; GPU tensors in:
   top1 and ranks stay int32 device tensors.  The ranking cache i2t / t2i serve from is neither read nor
   changed."""
-  if ties not in ('optimistic', 'pessimistic'):
-    raise ValueError("ties must be 'optimistic' or 'pessimistic', got %r" % (ties,))
+  _check_exact_options(ties, top1)
   if reduce not in ('max', 'mean'):
     raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
   on_device = isinstance(clip_embs, torch.Tensor) and clip_embs.is_cuda
@@ -1108,18 +1111,29 @@ def group_i2t_t2i_exact(clip_embs, cap_embs, num_clips, num_caps=None, reduce='m
   c = _as_device(clip_embs)
   s = _as_device(cap_embs, c.device)
   out = ops.group_rank_exact(c, s, num_clips, num_caps, reduce)
-  host = torch.stack(out).cpu().numpy().astype(numpy.float64)
+  tail = []
+  if top1 == 'exact':
+    ncaps = num_clips if num_caps is None else num_caps
+    _, top_v, res_v = ops.group_topk_exact(c, s, num_clips, ncaps, 1, 'v2p', reduce)
+    _, top_p, res_p = ops.group_topk_exact(c, s, num_clips, ncaps, 1, 'p2v', reduce)
+    out = out[:2] + (top_v.reshape(-1),) + out[3:6] + (top_p.reshape(-1),) + out[7:]
+    tail = [res_v, res_p]        # (per-query counts: summed on the host)
+  host = torch.stack(list(out) + tail).cpu().numpy().astype(numpy.float64)
   pick = 0 if ties == 'optimistic' else 1
   info, sides = {}, []
-  for name, h, dev in (('v2p', host[:4], out[:4]), ('p2v', host[4:], out[4:])):
+  for name, h, dev in (('v2p', host[:4], out[:4]), ('p2v', host[4:8], out[4:8])):
     info[name] = _exact_side_info(h)
     report = info[name]['report_lo' if pick == 0 else 'report_hi']
     sides.append((report, dev[2], dev[pick]) if on_device else (report, h[2], h[pick]))
   info['resolved'] = info['v2p']['resolved'] + info['p2v']['resolved']
+  if top1 == 'exact':
+    info['v2p']['top1_resolved'], info['p2v']['top1_resolved'] = int(host[8].sum()), int(host[9].sum())
+    info['top1_resolved'] = info['v2p']['top1_resolved'] + info['p2v']['top1_resolved']
   return sides[0], sides[1], info
 
 
-def group_retrieve(clip_embs, cap_embs, num_clips, num_caps=None, k=10, direction='p2v', reduce='max'):
+def group_retrieve(clip_embs, cap_embs, num_clips, num_caps=None, k=10, direction='p2v', reduce='max',
+                   exact=False):
   """Top-k retrieval by the group-wise score of the low level (group_i2t_t2i's score: block max of
   the clip x caption scores of a (video, paragraph) pair with max_violation, block mean without):
   direction 'p2v' gives the k best videos for every paragraph, 'v2p' the k best paragraphs for every
@@ -1133,7 +1147,14 @@ def group_retrieve(clip_embs, cap_embs, num_clips, num_caps=None, k=10, directio
 
   NumPy in, NumPy out: scores float32 [Bq, k] and index int64 [Bq, k].  GPU tensors in: device
   tensors out (float32, int32), on the current stream.  num_caps defaults to num_clips.  The ranking
-  cache i2t / t2i serve from is neither read nor changed."""
+  cache i2t / t2i serve from is neither read nor changed.
+
+  exact=True: the list of the FLOAT64 block scores of the same rows, certified (ops.group_topk_exact; the
+  block score of group_i2t_t2i_exact): its order and its membership at the k-th place depend on neither
+  summation order, tile shape nor machine, where the fp32 list differs on nearly every query once captions
+  are shared or clips nearly repeat.  scores are float64; the rest as above."""
+  if not isinstance(exact, (bool, numpy.bool_)):
+    raise ValueError('exact must be False or True, got %r' % (exact,))
   num_caps = num_clips if num_caps is None else num_caps
   if reduce not in ('max', 'mean'):
     raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
@@ -1147,7 +1168,10 @@ def group_retrieve(clip_embs, cap_embs, num_clips, num_caps=None, k=10, directio
   on_device = isinstance(clip_embs, torch.Tensor) and clip_embs.is_cuda
   c = _as_device(clip_embs)
   s = _as_device(cap_embs, c.device)
-  scores, index = ops.group_topk(c, s, num_clips, num_caps, k, direction, reduce)
+  if exact:
+    scores, index, _ = ops.group_topk_exact(c, s, num_clips, num_caps, k, direction, reduce)
+  else:
+    scores, index = ops.group_topk(c, s, num_clips, num_caps, k, direction, reduce)
   if on_device:
     return scores, index
   return scores.cpu().numpy(), index.cpu().numpy().astype(numpy.int64)

@@ -1217,6 +1217,16 @@ def group_topk_plan(num_clips, num_caps, n_clip_rows, n_cap_rows, k, direction='
   """The host plan of cmhse_group_topk_plan (int32 NumPy) for any video set (num_clips) and any
   paragraph set (num_caps); ValueError on a bad direction, a k outside [1, min(gallery groups, 128)],
   counts that do not tile the rows or a video / paragraph longer than 128 rows.  No GPU."""
+  return _group_topk_plan('cmhse_group_topk_plan', num_clips, num_caps, n_clip_rows, n_cap_rows, k, direction)
+
+
+def group_topk_exact_plan(num_clips, num_caps, n_clip_rows, n_cap_rows, k, direction='p2v'):
+  """The host plan of cmhse_group_topk_exact_plan: group_topk_plan's layout and ValueErrors, the query side
+  packed to the certified pass's (smaller) cap.  No GPU."""
+  return _group_topk_plan('cmhse_group_topk_exact_plan', num_clips, num_caps, n_clip_rows, n_cap_rows, k, direction)
+
+
+def _group_topk_plan(fn, num_clips, num_caps, n_clip_rows, n_cap_rows, k, direction):
   if direction not in _GROUP_DIRECTION:
     raise ValueError("direction must be 'p2v' or 'v2p', got %r" % (direction,))
   nclips = _group_counts(num_clips, 'num_clips')
@@ -1239,9 +1249,9 @@ def group_topk_plan(num_clips, num_caps, n_clip_rows, n_cap_rows, k, direction='
   np.cumsum(nclips, out=oc[1:])
   np.cumsum(ncaps, out=op[1:])
   plan = np.empty(_lib.group_topk_plan_max(Bv, Bp), dtype=np.int32)
-  n = _lib.load().cmhse_group_topk_plan(oc.ctypes.data, Bv, op.ctypes.data, Bp, _GROUP_DIRECTION[direction],
-                                        int(k), plan.ctypes.data, plan.size)
-  _lib.check(min(n, 0), 'cmhse_group_topk_plan')
+  n = getattr(_lib.load(), fn)(oc.ctypes.data, Bv, op.ctypes.data, Bp, _GROUP_DIRECTION[direction], int(k),
+                               plan.ctypes.data, plan.size)
+  _lib.check(min(n, 0), fn)
   return plan[:n]
 
 
@@ -1278,6 +1288,42 @@ def group_topk(clips, caps, num_clips, num_caps, k, direction='p2v', reduce='max
                             scores.data_ptr(), index.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
   _lib.check(rc, 'cmhse_group_topk')
   return scores, index
+
+
+def group_topk_exact(clips, caps, num_clips, num_caps, k, direction='p2v', reduce='max'):
+  """The k best gallery groups of every query group by the FLOAT64 block scores of group_topk's inputs,
+  certified (cmhse_group_topk_exact): device tensors (scores float64 [Bq, k], index int32 [Bq, k], resolved
+  int32 [Bq]) on the current stream.  The float64 score of a (video, paragraph) block is group_rank_exact's;
+  score descending, smaller gallery index first where two float64 scores are equal (group_topk's rule);
+  resolved is the number of gallery groups of each query that went through float64 (>= k).  The result
+  depends on neither summation order, tile shape nor machine.  group_topk's ValueErrors."""
+  if reduce not in _GROUP_REDUCE:
+    raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
+  if direction not in _GROUP_DIRECTION:
+    raise ValueError("direction must be 'p2v' or 'v2p', got %r" % (direction,))
+  for t, name in ((clips, 'clips'), (caps, 'caps')):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+      raise ValueError('%s must be a 2-D tensor' % name)
+  if clips.shape[1] != caps.shape[1]:
+    raise ValueError('embedding widths differ')
+  plan = group_topk_exact_plan(num_clips, num_caps, clips.shape[0], caps.shape[0], k, direction)
+  lib = _lib.load()
+  c = _f32c(clips, 'clips')
+  s = _f32c(caps, 'caps')
+  k = int(k)
+  Bq = int(plan[1] if direction == 'p2v' else plan[0])
+  scores = torch.empty(Bq, k, dtype=torch.float64, device=c.device)
+  index = torch.empty(Bq, k, dtype=torch.int32, device=c.device)
+  resolved = torch.empty(Bq, dtype=torch.int32, device=c.device)
+  ws_bytes = lib.cmhse_group_topk_exact_workspace(plan.ctypes.data, plan.size)
+  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=c.device)
+  plan_d = upload(plan, c.device)
+  rc = lib.cmhse_group_topk_exact(c.data_ptr(), s.data_ptr(), c.shape[0], s.shape[0], c.shape[1],
+                                  plan.ctypes.data, plan_d.data_ptr(), plan.size, _GROUP_DIRECTION[direction],
+                                  _GROUP_REDUCE[reduce], k, scores.data_ptr(), index.data_ptr(),
+                                  resolved.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+  _lib.check(rc, 'cmhse_group_topk_exact')
+  return scores, index, resolved
 
 
 def cosine_sim(im, s):

@@ -672,6 +672,59 @@ int cmhse_group_topk(const float* clips, const float* caps, int32_t Nc, int32_t 
                      int32_t reduce, int32_t K, float* scores /*[Bq,K]*/, int32_t* index /*[Bq,K]*/,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* Certified group-wise top-K retrieval: the K best gallery groups of every query group by the FLOAT64 block
+ * scores of the same fp32 rows, at about twice the cost of cmhse_group_topk plus one block64 per candidate.
+ * Inputs as for cmhse_group_topk: any video set against any paragraph set (Bv and Bp independent, every count
+ * 1..CMHSE_GROUP_TILE_ROWS rows), both directions, both reduce modes.  G64 is THE float64 block score of
+ * cmhse_group_rank_exact (exact64.hpp: block64, the same routine, the same bits).  For every query group q:
+ *   index[q, :]   the first K gallery groups in the order (G64 descending, then gallery index ascending): the
+ *                 tie rule of cmhse_group_topk, applied to the float64 scores.  Two scores that compare equal as
+ *                 doubles tie (-0.0 and +0.0 included);
+ *   scores[q, :]  those G64 values, float64;
+ *   resolved[q]   the gallery groups of query q that went through block64: a diagnostic, >= K, a function of
+ *                 the inputs and of the tunable "rank_exact_tol_scale" alone (nothing is skipped in a
+ *                 data-dependent way).
+ * How: (1) cmhse_group_topk, its kernels unchanged, into a private region of the workspace: G_K(q), the K-th
+ * fp32 block score of the query (first, so all it can refuse is refused before anything is launched); (2) one
+ * wave per clip and caption row: its norm, the largest norm of each side rounded up to fp32, and per query
+ * group tol_q = cmhse_group_rank_exact_tolerance(D, reduce, A_q, Bmax) x "rank_exact_tol_scale" rounded up to
+ * fp32 (A_q the largest norm of the query's rows, Bmax the largest of the gallery side: for p2v the paragraph's
+ * largest caption norm against the largest clip norm of the call); (3) a second pass of cmhse_group_topk's grid
+ * whose fp32 block scores are bit-identical to (1)'s: every gallery group with fl(G_K(q) - G32(q,g)) <= tol_q is
+ * a candidate, gets its block64 inside the tile that found it, and is merged into the query's list of K
+ * (float64 bits, index) pairs in LDS; (4) one wave per query merges the gallery panels' lists and sums their
+ * counts.  No list of pairs in memory, no capacity, no retry; nothing waits on another workgroup.
+ * Why it is exact: |G32(q,g) - G64(q,g)| <= E_q for every g (the bound of cmhse_group_rank_exact, row-wise for
+ * a video query, column-wise for a paragraph query; tol_q = 2 E_q (1 + 2^-18)).  The K groups of the fp32 list
+ * have G32 >= G_K, so the K-th largest G64 of the query is >= G_K - E_q; a member of the float64 top-K has G64 at
+ * least that (on a tie at the boundary too), so G32 >= G_K - 2 E_q: it is a candidate, and the exact top-K of a
+ * superset of the top-K is the top-K (derived in group.hip).
+ * Properties: the results do not depend on the tolerance as long as it is valid (the tunable only moves
+ * `resolved`; at 2^20 and D >= 16 every gallery group goes through float64), nor on tiling, panel count,
+ * scheduling or math mode; query subsets concatenate bit for bit.  Inputs are assumed finite.
+ *
+ * cmhse_group_topk_exact_plan (host only): cmhse_group_topk_plan's layout, arguments and errors; the query side
+ * is capped by THIS pass's LDS (a list entry is 12 bytes here, 8 there), by the same rule and never above
+ * cmhse_group_topk_plan's cap, so the plan serves the nested fp32 call too.  A plan of cmhse_group_topk_plan
+ * whose query tiles exceed the cap is refused by the two calls below (workspace 0, CMHSE_ERR_ARG).
+ * cmhse_group_topk_exact_workspace: bytes for the plan (0 for an invalid one), 256-byte aligned:
+ * cmhse_group_topk_workspace and that call's two outputs (8 bytes x Bq x K), 8 bytes per row of the query side,
+ * 4 per query group, and per gallery panel 12 bytes x Bq x K of pairs and 4 x Bq of counts.  The panel count
+ * follows cmhse_group_topk's rule with this pass's LDS size: fixed by the query side and K, not by the gallery
+ * (once the gallery has as many tiles as there are panels).
+ * Errors, before anything is launched, with the codes and in the order of cmhse_group_topk: CMHSE_ERR_ARG for a
+ * null pointer (scores / index / resolved / workspace included), Nc, Ns or D <= 0, a bad reduce, a plan that
+ * fails cmhse_group_topk's check, disagrees with the call or exceeds this pass's cap; CMHSE_ERR_WORKSPACE for a
+ * workspace that is unaligned (256 bytes) or too small; CMHSE_ERR_UNSUPPORTED for D >= 2^24 (the bound needs
+ * D u < 1). */
+int32_t cmhse_group_topk_exact_plan(const int32_t* clip_off_host, int32_t Bv, const int32_t* cap_off_host,
+                                    int32_t Bp, int32_t direction, int32_t K, int32_t* plan, int32_t plan_cap);
+size_t cmhse_group_topk_exact_workspace(const int32_t* plan_host, int32_t plan_len);
+int cmhse_group_topk_exact(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                           const int32_t* plan_host, const int32_t* plan, int32_t plan_len, int32_t direction,
+                           int32_t reduce, int32_t K, double* scores /*[Bq,K]*/, int32_t* index /*[Bq,K]*/,
+                           int32_t* resolved /*[Bq]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Replaces loss.cosine_sim (loss.py:12-13): scores[n,m] = im s^T, exact fp32. */
 int cmhse_cosine_sim(const float* im, const float* s, int32_t n, int32_t m, int32_t D,
                      float* scores, void* stream);
