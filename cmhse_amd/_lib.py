@@ -75,6 +75,10 @@ def group_topk_plan_max(Bv, Bp):
   return 2 * Bv + 2 * Bp + 12      # CMHSE_GROUP_TOPK_PLAN_MAX(Bv, Bp)
 
 
+def group_rank_labelled_plan_max(Bv, Bp, n_pairs):
+  return 3 * Bv + 3 * Bp + 2 * n_pairs + 16      # CMHSE_GROUP_RANK_LABELLED_PLAN_MAX(Bv, Bp, n_pairs)
+
+
 class StepLosses(ctypes.Structure):
   _fields_ = [('n_emb', c_int32), ('n_terms', c_int32), ('D', c_int32),
               ('x', c_void_p * STEP_LOSS_MAX), ('rows', c_int32 * STEP_LOSS_MAX),
@@ -160,6 +164,12 @@ SIGNATURES = {
     'cmhse_group_topk_exact': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                               c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_size_t, c_void_p]),
+    'cmhse_group_rank_labelled_plan': (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                                 c_int32, c_void_p, c_int32]),
+    'cmhse_group_rank_labelled_workspace': (c_size_t, [c_void_p, c_int32]),
+    'cmhse_group_rank_labelled': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                                 c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_size_t, c_void_p]),
     'cmhse_cosine_sim': (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                         c_void_p]),
     'cmhse_contrastive_workspace': (c_size_t, [c_int32]),

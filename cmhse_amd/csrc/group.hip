@@ -45,6 +45,21 @@
 //                             gallery group that G_K cannot rule out goes through block64 and into the query's
 //                             list of K (float64 bits, index) pairs in LDS (wave_merge_pairs);
 //   group_topk_exact_merge_kernel    merge_panel_pair_lists: the panels' lists and counts of each query.
+//
+// Labelled group-wise ranking (cmhse_group_rank_labelled: any video set, any paragraph set, any set of positive
+// gallery groups per query group; neither G nor the clip x caption matrix is stored):
+//   cmhse_group_rank_labelled_plan   host only: cmhse_group_topk_plan's tiles with the query side capped at
+//                             kGlQcap groups a tile, the labels (CSR, validated in full) and the PAIR TILES of
+//                             the threshold pass: the (query, positive) pairs in CSR order, whole pairs packed
+//                             greedily while both the clip rows and the caption rows of a tile stay <= 128;
+//   group_label_threshold_kernel   one workgroup per pair tile: the groups of its pairs gathered row by row
+//                             (an address per operand row, no copy), nt_phase, group_tile_reduce with the
+//                             tile's local offsets; only the diagonal blocks (pair k's query x pair k's
+//                             positive) are sunk, each into its query's 64-bit key by atomic max;
+//   group_label_count_kernel  group_topk_select_kernel's grid, tile loop and block reduction with a counting
+//                             epilogue: per query group a ballot of blk > thr and a popcount into a
+//                             per-(panel, query) count, and the running top-1 key;
+//   group_label_final_kernel  sums the counts and maxes the keys of the panels; decodes the threshold keys.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -1062,6 +1077,392 @@ int launch_group_sim(const float* clips, const float* caps, int32_t D, int32_t B
                       kGrSmem, stream, p);
 }
 
+
+// ---- labelled group-wise ranking (cmhse_group_rank_labelled) ----------------------------------------
+// rank[q] = #{ g : G(q, g) > thr[q] }, thr[q] = max over the positives p of query q of G(q, p), with G the block
+// score of group_sim_kernel / group_topk_select_kernel, bit for bit: both passes below take every block score
+// from nt_phase (each clip x caption score is its own MFMA k-chain: it depends on neither the row's place in the
+// tile nor the tile's other rows) and group_tile_reduce (one thread per block, clip-major then caption, fp64 sum
+// for the mean: a function of the block's scores alone).  So a threshold equals, bit for bit, the score the
+// counting pass computes for the same (query, positive) block, and the strict compare is exact.
+//
+// Counting pass LDS: the 40 KB tile buffers, then per query group its running top-1 key (8 bytes), its threshold
+// and its count (4 + 4) and a row of block scores of the current gallery tile (129 floats): 532 bytes a group.
+// There are no K lists, so the query cap is kGlQcap = 72 groups a tile (gt_qcap(1) is 64): 40960 + 72 x 532 =
+// 79264 bytes, the most that keeps TWO workgroups in a CU's 160 KB (the occupancy group_topk_select_kernel runs
+// at; the whole 128 groups of a tile would take 109 KB, one workgroup per CU).  The cap binds only where groups
+// average fewer than 1.8 rows; at val_1 (3.6 rows a group) the 128-row limit packs the query tiles.
+constexpr int kGlHdr = 10;             // plan header: Bv, Bp, Nc, Ns, direction, R, C, n_pairs, T pair tiles, query cap
+constexpr int kGlQcap = 72;            // query groups per query tile
+constexpr int kGlPairMax = CMHSE_GROUP_TILE_ROWS;   // pairs of a pair tile, at most (every group has a row)
+constexpr size_t kGlKeyOff = kGrSmem;                                            // score_key_t [kGlQcap]
+constexpr size_t kGlThrOff = kGlKeyOff + sizeof(score_key_t) * kGlQcap;          // float [kGlQcap]
+constexpr size_t kGlCntOff = kGlThrOff + sizeof(float) * kGlQcap;                // int [kGlQcap]
+constexpr size_t kGlBlkOff = kGlCntOff + sizeof(int32_t) * kGlQcap;              // float [kGlQcap][kGtBlkLd]
+constexpr size_t kGlCountSmem = kGlBlkOff + sizeof(float) * kGtBlkLd * kGlQcap;
+static_assert(2 * kGlCountSmem <= kGtLdsPerCU, "two counting workgroups per CU");
+// Threshold pass LDS behind the tile buffers (int32): the local clip / caption offsets of the tile's pairs
+// [129 each, padded to 132], the first clip row of each pair's video and the first caption row of its paragraph,
+// the pair's query and its positive [128 each], and the first wave's two scan totals.
+constexpr int kGlLd = kGlPairMax + 4;
+constexpr size_t kGlThresholdSmem = kGrSmem + sizeof(int32_t) * (2 * kGlLd + 4 * kGlPairMax + 4);
+
+struct GroupLabelParams {
+  const float* C;           // [Nc, D] clip rows
+  const float* S;           // [Ns, D] caption rows
+  int32_t D, use_max, p2v;
+  int32_t Bq, Bg, n_pairs;
+  int32_t q_tiles, g_tiles, panels;
+  const int32_t* clip_off;  // [Bv + 1] (device copy of the plan)
+  const int32_t* cap_off;   // [Bp + 1]
+  const int32_t* rt_vid;    // [R + 1] first video of each clip tile
+  const int32_t* ct_par;    // [C + 1] first paragraph of each caption tile
+  const int32_t* pos_off;   // [Bq + 1]
+  const int32_t* pos_idx;   // [n_pairs]
+  const int32_t* pt_pair;   // [T + 1] first pair of each pair tile
+  score_key_t* thrkey;      // [Bq] (zeroed)
+  int32_t* cnt;             // [panels, Bq]
+  score_key_t* key;         // [panels, Bq]
+  int32_t *rank, *top1, *best_pos;
+  float* best_score;        // or null
+};
+
+// One workgroup per pair tile.  Pair i of the tile (thread i) contributes the clip rows of its video and the
+// caption rows of its paragraph — the query's group on one side, the positive's on the other — so local video i
+// and local paragraph i are pair i's and the wanted blocks are the diagonal of the tile's np x np blocks.  A
+// group that occurs in several pairs is simply gathered again.  The plan keeps the rows of either side <= 128.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void group_label_threshold_kernel(const GroupLabelParams p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  int32_t* s_lv = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(smem) + kGrSmem);   // [np + 1]
+  int32_t* s_lp = s_lv + kGlLd;                                                          // [np + 1]
+  int32_t* s_vrow = s_lp + kGlLd;
+  int32_t* s_prow = s_vrow + kGlPairMax;
+  int32_t* s_query = s_prow + kGlPairMax;
+  int32_t* s_pos = s_query + kGlPairMax;
+  int32_t* s_tot = s_pos + kGlPairMax;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, srow = tid >> 2;
+  const int k0 = p.pt_pair[blockIdx.x];
+  int np = p.pt_pair[blockIdx.x + 1] - k0;
+  np = np > kGlPairMax ? kGlPairMax : np;   // (validated on the host copy)
+  if (np <= 0) return;                      // (workgroup-uniform, no barrier passed)
+  int cv = 0, cp = 0;
+  if (tid < np) {
+    const int k = k0 + tid;
+    // The query of pair k: the last q with pos_off[q] <= k.  Every list holds a positive, so q lies in
+    // [k - (n_pairs - Bq), k]; every index read lies in [0, Bq), whatever the device copy holds.
+    int lo = k - (p.n_pairs - p.Bq), hi = (k < p.Bq - 1) ? k : p.Bq - 1;
+    lo = lo < 0 ? 0 : lo;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (p.pos_off[mid] <= k) lo = mid; else hi = mid - 1;
+    }
+    int g = p.pos_idx[k];
+    g = g < 0 ? 0 : (g < p.Bg ? g : p.Bg - 1);   // (validated on the host copy)
+    const int v = p.p2v ? g : lo, par = p.p2v ? lo : g;
+    const int c0 = p.clip_off[v], s0 = p.cap_off[par];
+    cv = p.clip_off[v + 1] - c0;
+    cp = p.cap_off[par + 1] - s0;
+    s_vrow[tid] = c0;
+    s_prow[tid] = s0;
+    s_query[tid] = lo;
+    s_pos[tid] = g;
+  }
+  // inclusive scans of the two row counts over the tile's pairs (threads 0..127: two waves)
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const int a = __shfl_up(cv, s, 64), b = __shfl_up(cp, s, 64);
+    if (lane >= s) {
+      cv += a;
+      cp += b;
+    }
+  }
+  if (tid == 63) {
+    s_tot[0] = cv;
+    s_tot[1] = cp;
+  }
+  __syncthreads();
+  if (wave == 1) {
+    cv += s_tot[0];
+    cp += s_tot[1];
+  }
+  if (tid < kGlPairMax) {
+    s_lv[tid + 1] = cv;
+    s_lp[tid + 1] = cp;
+  }
+  if (tid == 0) {
+    s_lv[0] = 0;
+    s_lp[0] = 0;
+  }
+  __syncthreads();
+  const int nr = s_lv[np], nc = s_lp[np];
+  const int my_voff = (tid <= np) ? s_lv[tid] : 0;
+  const int my_poff = (tid <= np) ? s_lp[tid] : 0;
+  // operand rows: local row r belongs to the pair j with s_l*[j] <= r < s_l*[j + 1]
+  rowaddr_t ar[kGrBM / 64], br[kGrBN / 64];
+  bool av[kGrBM / 64], bv[kGrBN / 64];
+#pragma unroll
+  for (int i = 0; i < kGrBM / 64; ++i) {
+    const int r = srow + 64 * i;
+    av[i] = r < nr;
+    int row = 0;
+    if (av[i]) {
+      int lo = 0, hi = np - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s_lv[mid] <= r) lo = mid; else hi = mid - 1;
+      }
+      row = s_vrow[lo] + r - s_lv[lo];
+    }
+    ar[i] = row_addr(p.C + static_cast<int64_t>(row) * p.D);
+  }
+#pragma unroll
+  for (int i = 0; i < kGrBN / 64; ++i) {
+    const int r = srow + 64 * i;
+    bv[i] = r < nc;
+    int row = 0;
+    if (bv[i]) {
+      int lo = 0, hi = np - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s_lp[mid] <= r) lo = mid; else hi = mid - 1;
+      }
+      row = s_prow[lo] + r - s_lp[lo];
+    }
+    br[i] = row_addr(p.S + static_cast<int64_t>(row) * p.D);
+  }
+  f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
+  const int b_row0[2] = {wn * 64, wn * 64 + 32};
+  nt_phase<kGrBM, kGrBN, 2, 2, 2, 1, VEC>(smem, ar, av, br, bv, p.D, wm * 64, b_row0, acc);
+  group_tile_reduce(smem, acc, np, np, nr, my_voff, my_poff, p.use_max, [&](int v, int q, float g) {
+    if (v == q) atomicMax(&p.thrkey[s_query[v]], score_key(g, s_pos[v]));
+  });
+}
+
+// group_topk_select_kernel's grid (panel_work restates its walk), tile loop and block reduction; the epilogue
+// counts.  Wave w owns the query groups w, w + 4, ... of the tile through every gallery tile of the panel, so
+// their running words in LDS have one writer.  The top-1 key is reduced over the wave only when some lane beats
+// the running key (after the first tiles almost never).
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void group_label_count_kernel(const GroupLabelParams p) {
+  const PanelWork w = panel_work(blockIdx.x, gridDim.x, p.q_tiles, p.g_tiles, p.panels);
+  if (w.panel < 0) return;   // padding of the grid to a multiple of 8
+  const int panel = w.panel, qt = w.row_tile;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, srow = tid >> 2;
+  const int32_t* q_start = p.p2v ? p.ct_par : p.rt_vid;
+  const int32_t* g_start = p.p2v ? p.rt_vid : p.ct_par;
+  const int qg0 = q_start[qt], nQ = q_start[qt + 1] - qg0;   // nQ <= kGlQcap: the plan is checked
+
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  char* lds = reinterpret_cast<char*>(smem);
+  score_key_t* s_key = reinterpret_cast<score_key_t*>(lds + kGlKeyOff);
+  float* s_thr = reinterpret_cast<float*>(lds + kGlThrOff);
+  int32_t* s_cnt = reinterpret_cast<int32_t*>(lds + kGlCntOff);
+  float* blk = reinterpret_cast<float*>(lds + kGlBlkOff);   // [nQ][kGtBlkLd]
+  if (tid < nQ) {   // (seen after nt_phase's barriers; every panel has a tile: panels <= g_tiles)
+    s_key[tid] = 0ull;
+    s_cnt[tid] = 0;
+    s_thr[tid] = key_score(p.thrkey[qg0 + tid]);
+  }
+
+  const int b_row0[2] = {wn * 64, wn * 64 + 32};
+  for (int t = w.t_begin; t < w.t_end; ++t) {
+    const int gg0 = g_start[t], nG = g_start[t + 1] - gg0;
+    const int v0 = p.p2v ? gg0 : qg0, nv = p.p2v ? nG : nQ;
+    const int q0 = p.p2v ? qg0 : gg0, nq = p.p2v ? nQ : nG;
+    const int r_begin = p.clip_off[v0], nr = p.clip_off[v0 + nv] - r_begin;
+    const int c_begin = p.cap_off[q0], nc = p.cap_off[q0 + nq] - c_begin;
+    const int my_voff = (tid <= nv) ? p.clip_off[v0 + tid] - r_begin : 0;
+    const int my_poff = (tid <= nq) ? p.cap_off[q0 + tid] - c_begin : 0;
+    rowaddr_t ar[kGrBM / 64], br[kGrBN / 64];
+    bool av[kGrBM / 64], bv[kGrBN / 64];
+#pragma unroll
+    for (int i = 0; i < kGrBM / 64; ++i) ar[i] = tile_row(p.C, p.D, r_begin, srow + 64 * i, nr, &av[i]);
+#pragma unroll
+    for (int i = 0; i < kGrBN / 64; ++i) br[i] = tile_row(p.S, p.D, c_begin, srow + 64 * i, nc, &bv[i]);
+    f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
+    // ends with a barrier: every wave is done with the tile buffers (and with the previous tile's
+    // counting, so blk is free)
+    nt_phase<kGrBM, kGrBN, 2, 2, 2, 1, VEC>(smem, ar, av, br, bv, p.D, wm * 64, b_row0, acc);
+    const bool p2v = p.p2v;
+    group_tile_reduce(smem, acc, nv, nq, nr, my_voff, my_poff, p.use_max, [&](int v, int q, float g) {
+      blk[p2v ? q * kGtBlkLd + v : v * kGtBlkLd + q] = g;
+    });
+    for (int qi = wave; qi < nQ; qi += kThreads / 64) {   // (wave-uniform)
+      const float* row = blk + qi * kGtBlkLd;
+      const float thr = s_thr[qi];
+      const bool in0 = lane < nG, in1 = lane + 64 < nG;   // (slots past nG hold an earlier tile's scores)
+      const float x0 = row[lane], x1 = row[lane + 64];
+      const int c = __popcll(__ballot(in0 && x0 > thr)) + __popcll(__ballot(in1 && x1 > thr));
+      const score_key_t k0 = in0 ? score_key(x0, gg0 + lane) : 0ull;
+      const score_key_t k1 = in1 ? score_key(x1, gg0 + lane + 64) : 0ull;
+      score_key_t best = k0 > k1 ? k0 : k1;
+      const bool beats = __ballot(best > s_key[qi]) != 0ull;
+      if (beats) {
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+          const unsigned hi = __shfl_xor(static_cast<unsigned>(best >> 32), s, 64);
+          const unsigned lo = __shfl_xor(static_cast<unsigned>(best), s, 64);
+          const score_key_t o = (static_cast<score_key_t>(hi) << 32) | lo;
+          best = o > best ? o : best;
+        }
+      }
+      if (lane == 0) {
+        if (beats) s_key[qi] = best;
+        s_cnt[qi] += c;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < nQ) {
+    const int64_t e = static_cast<int64_t>(panel) * p.Bq + qg0 + tid;
+    p.cnt[e] = s_cnt[tid];
+    p.key[e] = s_key[tid];
+  }
+}
+
+// thread q < Bq: the panels' counts summed and keys maxed (integers: no order), the threshold key decoded
+__global__ void group_label_final_kernel(const GroupLabelParams p) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= p.Bq) return;
+  int c = 0;
+  score_key_t k = 0;
+  for (int P = 0; P < p.panels; ++P) {
+    const int64_t e = static_cast<int64_t>(P) * p.Bq + q;
+    c += p.cnt[e];
+    k = p.key[e] > k ? p.key[e] : k;
+  }
+  const score_key_t tk = p.thrkey[q];
+  p.rank[q] = c;
+  p.top1[q] = key_index(k);
+  p.best_pos[q] = key_index(tk);
+  if (p.best_score) p.best_score[q] = key_score(tk);
+}
+
+// ---- cmhse_group_rank_labelled: its plan, its check and its workspace ----
+// Layout (int32): the header (kGlHdr words), clip_off[Bv+1], cap_off[Bp+1], the first video of each clip tile
+// [R+1], the first paragraph of each caption tile [C+1], pos_off[Bq+1], pos_idx[n_pairs], the first pair of
+// each pair tile [T+1].
+struct GlPlan {
+  int32_t Bv, Bp, R, Cc, Bq, Bg, n_pairs, T;
+  size_t clip_off, cap_off, rt, ct, pos_off, pos_idx, pt, len;   // word offsets
+};
+
+GlPlan gl_layout(int32_t Bv, int32_t Bp, int32_t direction, int32_t R, int32_t Cc, int32_t n_pairs, int32_t T) {
+  GlPlan L;
+  L.Bv = Bv, L.Bp = Bp, L.R = R, L.Cc = Cc, L.n_pairs = n_pairs, L.T = T;
+  L.Bq = direction == CMHSE_GROUP_P2V ? Bp : Bv;
+  L.Bg = direction == CMHSE_GROUP_P2V ? Bv : Bp;
+  size_t o = kGlHdr;
+  L.clip_off = o, o += static_cast<size_t>(Bv) + 1;
+  L.cap_off = o, o += static_cast<size_t>(Bp) + 1;
+  L.rt = o, o += static_cast<size_t>(R) + 1;
+  L.ct = o, o += static_cast<size_t>(Cc) + 1;
+  L.pos_off = o, o += static_cast<size_t>(L.Bq) + 1;
+  L.pos_idx = o, o += static_cast<size_t>(n_pairs);
+  L.pt = o, o += static_cast<size_t>(T) + 1;
+  L.len = o;
+  return L;
+}
+
+// the labels in full: 0 first, every list non-empty, n_pairs last, every index in [0, Bg)
+bool labels_ok(const int32_t* pos_off, const int32_t* pos_idx, int32_t Bq, int32_t Bg, int32_t n_pairs) {
+  if (n_pairs < Bq || pos_off[0] != 0 || pos_off[Bq] != n_pairs) return false;
+  for (int32_t q = 0; q < Bq; ++q)
+    if (pos_off[q + 1] <= pos_off[q]) return false;
+  for (int32_t e = 0; e < n_pairs; ++e)
+    if (pos_idx[e] < 0 || pos_idx[e] >= Bg) return false;
+  return true;
+}
+
+// The pair tiles: whole pairs in CSR order, a tile closed when the next pair would take its clip rows or its
+// caption rows past 128 (every group has at most 128 rows: a pair alone always fits).  start == nullptr only
+// counts.  pair_tiles_ok accepts any cut that respects the limits, greedy or not.
+int32_t pair_tiles(const int32_t* clip_off, const int32_t* cap_off, bool p2v, const int32_t* pos_off,
+                   const int32_t* pos_idx, int32_t Bq, int32_t* start) {
+  int32_t T = 0, k = 0;
+  int rows_v = 0, rows_p = 0;
+  for (int32_t q = 0; q < Bq; ++q)
+    for (int32_t e = pos_off[q]; e < pos_off[q + 1]; ++e, ++k) {
+      const int32_t v = p2v ? pos_idx[e] : q, par = p2v ? q : pos_idx[e];
+      const int nv = clip_off[v + 1] - clip_off[v], npar = cap_off[par + 1] - cap_off[par];
+      if (k == 0 || rows_v + nv > kGrBM || rows_p + npar > kGrBN) {
+        if (start) start[T] = k;
+        ++T;
+        rows_v = rows_p = 0;
+      }
+      rows_v += nv;
+      rows_p += npar;
+    }
+  if (start) start[T] = k;
+  return T;
+}
+
+bool pair_tiles_ok(const int32_t* clip_off, const int32_t* cap_off, bool p2v, const int32_t* pos_off,
+                   const int32_t* pos_idx, int32_t Bq, int32_t n_pairs, const int32_t* start, int32_t T) {
+  if (T < 1 || T > n_pairs || start[0] != 0 || start[T] != n_pairs) return false;
+  for (int32_t t = 0; t < T; ++t)
+    if (start[t + 1] <= start[t]) return false;
+  int32_t t = 0, k = 0;
+  int rows_v = 0, rows_p = 0;
+  for (int32_t q = 0; q < Bq; ++q)
+    for (int32_t e = pos_off[q]; e < pos_off[q + 1]; ++e, ++k) {
+      if (k == start[t + 1]) {
+        ++t;
+        rows_v = rows_p = 0;
+      }
+      const int32_t v = p2v ? pos_idx[e] : q, par = p2v ? q : pos_idx[e];
+      rows_v += clip_off[v + 1] - clip_off[v];
+      rows_p += cap_off[par + 1] - cap_off[par];
+      if (rows_v > kGrBM || rows_p > kGrBN) return false;
+    }
+  return true;
+}
+
+// The host plan checked in full (O(Bv + Bp + n_pairs)) against the call: what the kernels trust — tile rows
+// within the tile buffers, query groups per tile within the LDS words, labels inside the gallery, pair tiles
+// within 128 rows either side.
+bool gl_plan_ok(const int32_t* ph, int32_t len, int32_t Nc, int32_t Ns, int32_t direction) {
+  if (!ph || len < kGlHdr) return false;
+  const int32_t Bv = ph[0], Bp = ph[1], R = ph[5], Cc = ph[6], n_pairs = ph[7], T = ph[8];
+  if (Bv < 1 || Bp < 1 || ph[2] != Nc || ph[3] != Ns || ph[4] != direction || ph[9] != kGlQcap) return false;
+  if (direction != CMHSE_GROUP_P2V && direction != CMHSE_GROUP_V2P) return false;
+  if (R < 1 || R > Bv || Cc < 1 || Cc > Bp || n_pairs < 1 || T < 1 || T > n_pairs) return false;
+  const GlPlan L = gl_layout(Bv, Bp, direction, R, Cc, n_pairs, T);
+  if (static_cast<size_t>(len) != L.len) return false;
+  const bool p2v = direction == CMHSE_GROUP_P2V;
+  return offsets_ok(ph + L.clip_off, Bv) && offsets_ok(ph + L.cap_off, Bp) && ph[L.clip_off + Bv] == Nc &&
+         ph[L.cap_off + Bp] == Ns && tiles_ok(ph + L.rt, R, ph + L.clip_off, Bv, kGrBM, p2v ? 0x7fffffff : kGlQcap) &&
+         tiles_ok(ph + L.ct, Cc, ph + L.cap_off, Bp, kGrBN, p2v ? kGlQcap : 0x7fffffff) &&
+         labels_ok(ph + L.pos_off, ph + L.pos_idx, L.Bq, L.Bg, n_pairs) &&
+         pair_tiles_ok(ph + L.clip_off, ph + L.cap_off, p2v, ph + L.pos_off, ph + L.pos_idx, L.Bq, n_pairs,
+                       ph + L.pt, T);
+}
+
+// (plan_host: gl_plan_ok has passed)
+GlPlan gl_plan_of(const int32_t* ph) { return gl_layout(ph[0], ph[1], ph[4], ph[5], ph[6], ph[7], ph[8]); }
+
+int32_t gl_panels(const GlPlan& L, bool p2v) {
+  return gt_panels_for_smem(p2v ? L.Cc : L.R, p2v ? L.R : L.Cc, kGlCountSmem);
+}
+
+// the threshold keys [Bq], then one count and one key per (panel, query group)
+struct GlWs {
+  size_t thrkey, cnt, key, total;
+};
+GlWs gl_ws(int32_t Bq, int32_t panels) {
+  const size_t part = static_cast<size_t>(panels) * static_cast<size_t>(Bq);
+  GlWs W;
+  size_t off = 0;
+  W.thrkey = off, off += align256(static_cast<size_t>(Bq) * sizeof(score_key_t));
+  W.cnt = off, off += align256(part * sizeof(int32_t));
+  W.key = off, off += align256(part * sizeof(score_key_t));
+  W.total = off;
+  return W;
+}
+
 }  // namespace
 }  // namespace cmhse
 
@@ -1425,5 +1826,115 @@ extern "C" int cmhse_group_topk_exact(const float* clips, const float* caps, int
   if (rc != CMHSE_OK) return rc;
   const PanelPairLists lists = {pp.ws_bits, pp.ws_idx, pp.ws_count, p.panels, p.Bq, K, scores, index, resolved};
   hipLaunchKernelGGL(group_topk_exact_merge_kernel, dim3((p.Bq + 3) / 4), dim3(kThreads), 0, stream, lists);
+  return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
+}
+
+extern "C" int32_t cmhse_group_rank_labelled_plan(const int32_t* clip_off_host, int32_t Bv,
+                                                  const int32_t* cap_off_host, int32_t Bp, int32_t direction,
+                                                  const int32_t* pos_off_host, const int32_t* pos_idx_host,
+                                                  int32_t n_pairs, int32_t* plan, int32_t plan_cap) {
+  if (!clip_off_host || !cap_off_host || !pos_off_host || !pos_idx_host || !plan || Bv <= 0 || Bp <= 0)
+    return CMHSE_ERR_ARG;
+  if (direction != CMHSE_GROUP_P2V && direction != CMHSE_GROUP_V2P) return CMHSE_ERR_ARG;
+  if (!offsets_ok(clip_off_host, Bv) || !offsets_ok(cap_off_host, Bp)) return CMHSE_ERR_ARG;
+  const bool p2v = direction == CMHSE_GROUP_P2V;
+  const int32_t Bq = p2v ? Bp : Bv, Bg = p2v ? Bv : Bp;
+  if (!labels_ok(pos_off_host, pos_idx_host, Bq, Bg, n_pairs)) return CMHSE_ERR_ARG;
+  for (int32_t b = 0; b < Bv; ++b)
+    if (clip_off_host[b + 1] - clip_off_host[b] > kGrBM) return CMHSE_ERR_UNSUPPORTED;
+  for (int32_t b = 0; b < Bp; ++b)
+    if (cap_off_host[b + 1] - cap_off_host[b] > kGrBN) return CMHSE_ERR_UNSUPPORTED;
+  const int64_t need =
+      3 * static_cast<int64_t>(Bv) + 3 * static_cast<int64_t>(Bp) + 2 * static_cast<int64_t>(n_pairs) + 16;
+  if (need > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  if (plan_cap < need) return CMHSE_ERR_WORKSPACE;   // CMHSE_GROUP_RANK_LABELLED_PLAN_MAX
+  // the offsets and the tiles first: the places of the labels and the pair tiles follow from R and C
+  int32_t* clip_off = plan + kGlHdr;
+  int32_t* cap_off = clip_off + Bv + 1;
+  for (int32_t b = 0; b <= Bv; ++b) clip_off[b] = clip_off_host[b];
+  for (int32_t b = 0; b <= Bp; ++b) cap_off[b] = cap_off_host[b];
+  int32_t* rt = cap_off + Bp + 1;
+  const int32_t R = pack(clip_off, Bv, kGrBM, rt, p2v ? 0x7fffffff : kGlQcap);
+  int32_t* ctp = rt + R + 1;
+  const int32_t Cc = pack(cap_off, Bp, kGrBN, ctp, p2v ? kGlQcap : 0x7fffffff);
+  const int32_t T = pair_tiles(clip_off, cap_off, p2v, pos_off_host, pos_idx_host, Bq, nullptr);
+  const GlPlan L = gl_layout(Bv, Bp, direction, R, Cc, n_pairs, T);
+  for (int32_t q = 0; q <= Bq; ++q) plan[L.pos_off + q] = pos_off_host[q];
+  for (int32_t e = 0; e < n_pairs; ++e) plan[L.pos_idx + e] = pos_idx_host[e];
+  pair_tiles(clip_off, cap_off, p2v, pos_off_host, pos_idx_host, Bq, plan + L.pt);
+  plan[0] = Bv;
+  plan[1] = Bp;
+  plan[2] = clip_off_host[Bv];
+  plan[3] = cap_off_host[Bp];
+  plan[4] = direction;
+  plan[5] = R;
+  plan[6] = Cc;
+  plan[7] = n_pairs;
+  plan[8] = T;
+  plan[9] = kGlQcap;
+  return static_cast<int32_t>(L.len);
+}
+
+extern "C" size_t cmhse_group_rank_labelled_workspace(const int32_t* plan_host, int32_t plan_len_) {
+  if (!plan_host || plan_len_ < kGlHdr || !gl_plan_ok(plan_host, plan_len_, plan_host[2], plan_host[3], plan_host[4]))
+    return 0;
+  const GlPlan L = gl_plan_of(plan_host);
+  return gl_ws(L.Bq, gl_panels(L, plan_host[4] == CMHSE_GROUP_P2V)).total;
+}
+
+extern "C" int cmhse_group_rank_labelled(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                                         const int32_t* plan_host, const int32_t* plan, int32_t plan_len_,
+                                         int32_t direction, int32_t reduce, int32_t* rank, int32_t* top1,
+                                         int32_t* best_pos, float* best_score, void* workspace,
+                                         size_t workspace_bytes, void* stream_) {
+  if (!clips || !caps || !plan_host || !plan || !rank || !top1 || !best_pos || !workspace) return CMHSE_ERR_ARG;
+  if (Nc <= 0 || Ns <= 0 || D <= 0) return CMHSE_ERR_ARG;
+  if (reduce != CMHSE_GROUP_MAX && reduce != CMHSE_GROUP_MEAN) return CMHSE_ERR_ARG;
+  if (!gl_plan_ok(plan_host, plan_len_, Nc, Ns, direction)) return CMHSE_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0 ||
+      workspace_bytes < cmhse_group_rank_labelled_workspace(plan_host, plan_len_))
+    return CMHSE_ERR_WORKSPACE;
+  const GlPlan L = gl_plan_of(plan_host);
+  GroupLabelParams p;
+  p.C = clips;
+  p.S = caps;
+  p.D = D;
+  p.use_max = reduce == CMHSE_GROUP_MAX;
+  p.p2v = direction == CMHSE_GROUP_P2V;
+  p.Bq = L.Bq;
+  p.Bg = L.Bg;
+  p.n_pairs = L.n_pairs;
+  p.q_tiles = p.p2v ? L.Cc : L.R;
+  p.g_tiles = p.p2v ? L.R : L.Cc;
+  p.panels = gl_panels(L, p.p2v != 0);
+  p.clip_off = plan + L.clip_off;
+  p.cap_off = plan + L.cap_off;
+  p.rt_vid = plan + L.rt;
+  p.ct_par = plan + L.ct;
+  p.pos_off = plan + L.pos_off;
+  p.pos_idx = plan + L.pos_idx;
+  p.pt_pair = plan + L.pt;
+  const GlWs W = gl_ws(L.Bq, p.panels);
+  char* const ws = static_cast<char*>(workspace);
+  p.thrkey = reinterpret_cast<score_key_t*>(ws + W.thrkey);
+  p.cnt = reinterpret_cast<int32_t*>(ws + W.cnt);
+  p.key = reinterpret_cast<score_key_t*>(ws + W.key);
+  p.rank = rank;
+  p.top1 = top1;
+  p.best_pos = best_pos;
+  p.best_score = best_score;
+  const int64_t blocks = panel_grid_blocks(p.q_tiles, p.panels);
+  if (blocks > 0x7fffffffLL) return CMHSE_ERR_UNSUPPORTED;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (hipMemsetAsync(p.thrkey, 0, sizeof(score_key_t) * static_cast<size_t>(L.Bq), stream) != hipSuccess)
+    return CMHSE_ERR_LAUNCH;
+  // 1. the thresholds, 2. the counts and top-1 keys of each panel, 3. the panels combined
+  int rc = launch_tiles(group_label_threshold_kernel<true>, group_label_threshold_kernel<false>, D,
+                        dim3(static_cast<unsigned>(L.T)), kGlThresholdSmem, stream, p);
+  if (rc != CMHSE_OK) return rc;
+  rc = launch_tiles(group_label_count_kernel<true>, group_label_count_kernel<false>, D,
+                    dim3(static_cast<unsigned>(blocks)), kGlCountSmem, stream, p);
+  if (rc != CMHSE_OK) return rc;
+  hipLaunchKernelGGL(group_label_final_kernel, dim3((L.Bq + 255) / 256), dim3(256), 0, stream, p);
   return (hipGetLastError() == hipSuccess) ? CMHSE_OK : CMHSE_ERR_LAUNCH;
 }

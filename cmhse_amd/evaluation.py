@@ -1264,6 +1264,73 @@ def i2t_t2i_labelled(images, captions, pairs):
           (report_from_ranks(host[2]), host[3], host[2]))
 
 
+def _group_labelled_args(clip_embs, cap_embs, reduce):
+  if reduce not in ('max', 'mean'):
+    raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
+  for x, name in ((clip_embs, 'clip_embs'), (cap_embs, 'cap_embs')):
+    if len(getattr(x, 'shape', ())) != 2:
+      raise ValueError('%s must be 2-D' % name)
+  if clip_embs.shape[1] != cap_embs.shape[1]:
+    raise ValueError('embedding widths differ')
+
+
+def group_rank_labelled(clip_embs, cap_embs, num_clips, num_caps, positives, direction='p2v', reduce='max'):
+  """rank_labelled by the group-wise score of the low level (group_i2t_t2i's score) for any video set
+  (clip rows, num_clips), any paragraph set (caption rows, num_caps) and any set of correct answers per
+  query: direction 'p2v' ranks the videos for every paragraph, 'v2p' the paragraphs for every video, and
+  `positives` gives, for every query group, the gallery groups that count as correct (ops.positives_csr's
+  forms).  The rank of a query is the rank of its best-placed positive (ops.group_rank_labelled:
+  matrix-free, exact fp32).  Returns (report, top1, ranks) in i2t's format (report_from_ranks; float64
+  NumPy).  GPU tensors in: top1 and ranks stay int32 device tensors.  The ranking cache i2t / t2i serve
+  from is neither read nor changed."""
+  _group_labelled_args(clip_embs, cap_embs, reduce)
+  # argument errors before the upload
+  ops.group_rank_labelled_plan(num_clips, num_caps, len(clip_embs), len(cap_embs), positives, direction)
+  on_device = isinstance(clip_embs, torch.Tensor) and clip_embs.is_cuda
+  c = _as_device(clip_embs)
+  s = _as_device(cap_embs, c.device)
+  rank, top1, _ = ops.group_rank_labelled(c, s, num_clips, num_caps, positives, direction, reduce)
+  host = torch.stack([rank, top1]).cpu().numpy().astype(numpy.float64)
+  if on_device:
+    return report_from_ranks(host[0]), top1, rank
+  return report_from_ranks(host[0]), host[1], host[0]
+
+
+def group_i2t_t2i_labelled(clip_embs, cap_embs, num_clips, num_caps, pairs, reduce='max'):
+  """group_i2t_t2i for a video set and a paragraph set whose correct answers are given by `pairs`, an
+  integer [P, 2] array of (video, paragraph) — any number of groups on either side, any number of correct
+  partners per group, at least one (pairs_from_ids builds it from two id lists).  Two annotation sets
+  scored against one video set at the low level:
+
+    _, _, clip, cap1, _, _, nclips, ids1 = encode_data(opt, model, val_1_loader)
+    _, _, _,    cap2, _, _, ncaps2, ids2 = encode_data(opt, model, val_2_loader)
+    caps = numpy.concatenate([cap1, cap2])
+    (r_v2p, _, _), (r_p2v, _, _) = group_i2t_t2i_labelled(
+        clip, caps, nclips, list(nclips) + list(ncaps2), pairs_from_ids(ids1, ids1 + ids2))
+
+  Returns ((report, top1, ranks) video -> paragraph, the same paragraph -> video), each in i2t's format,
+  with one device-to-host copy; with a square problem and pairs (i, i) exactly what group_i2t_t2i returns.
+  GPU tensors in: top1 and ranks stay int32 device tensors.  The ranking cache i2t / t2i serve from is
+  neither read nor changed."""
+  _group_labelled_args(clip_embs, cap_embs, reduce)
+  nv = len(num_clips)
+  npar = len(num_caps)
+  csr_v, csr_p = csr_from_pairs(pairs, nv, npar)   # argument errors before the upload
+  ops.group_rank_labelled_plan(num_clips, num_caps, len(clip_embs), len(cap_embs), csr_v, 'v2p')
+  on_device = isinstance(clip_embs, torch.Tensor) and clip_embs.is_cuda
+  c = _as_device(clip_embs)
+  s = _as_device(cap_embs, c.device)
+  r_v, t_v, _ = ops.group_rank_labelled(c, s, num_clips, num_caps, csr_v, 'v2p', reduce)
+  r_p, t_p, _ = ops.group_rank_labelled(c, s, num_clips, num_caps, csr_p, 'p2v', reduce)
+  # (the two sides differ in length: one flat vector, cut on the host)
+  n, m = r_v.numel(), r_p.numel()
+  host = numpy.split(torch.cat([r_v, t_v, r_p, t_p]).cpu().numpy().astype(numpy.float64), [n, 2 * n, 2 * n + m])
+  if on_device:
+    return ((report_from_ranks(host[0]), t_v, r_v), (report_from_ranks(host[2]), t_p, r_p))
+  return ((report_from_ranks(host[0]), host[1], host[0]),
+          (report_from_ranks(host[2]), host[3], host[2]))
+
+
 def i2t_t2i_exact(images, captions, ties='optimistic', top1='fp32'):
   """i2t_t2i on the ranks of the FLOAT64 scores of the two matrices, certified (ops.sim_rank_exact):
   independent of summation order, tile shape and machine, where the fp32 ranks of i2t / t2i differ from

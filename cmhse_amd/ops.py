@@ -1326,6 +1326,82 @@ def group_topk_exact(clips, caps, num_clips, num_caps, k, direction='p2v', reduc
   return scores, index, resolved
 
 
+def group_rank_labelled_plan(num_clips, num_caps, n_clip_rows, n_cap_rows, positives, direction='p2v'):
+  """The host plan of cmhse_group_rank_labelled_plan (int32 NumPy) for any video set (num_clips), any
+  paragraph set (num_caps) and the labels `positives` (positives_csr's forms, one list of gallery GROUPS
+  per query group: direction 'p2v' lists videos per paragraph, 'v2p' paragraphs per video).  ValueError on
+  a bad direction, counts that do not tile the rows, a video / paragraph longer than 128 rows, and
+  positives_csr's ValueErrors, which name the offending query.  No GPU."""
+  if direction not in _GROUP_DIRECTION:
+    raise ValueError("direction must be 'p2v' or 'v2p', got %r" % (direction,))
+  nclips = _group_counts(num_clips, 'num_clips')
+  ncaps = _group_counts(num_caps, 'num_caps')
+  if int(nclips.sum()) != n_clip_rows or int(ncaps.sum()) != n_cap_rows:
+    raise ValueError('the counts must tile the rows: sum(num_clips) = %d for %d clip rows, '
+                     'sum(num_caps) = %d for %d caption rows'
+                     % (nclips.sum(), n_clip_rows, ncaps.sum(), n_cap_rows))
+  longest = max(int(nclips.max()), int(ncaps.max()))
+  if longest > _lib.GROUP_TILE_ROWS:
+    raise ValueError('a video or paragraph of %d rows: group scores support at most %d'
+                     % (longest, _lib.GROUP_TILE_ROWS))
+  Bv, Bp = nclips.size, ncaps.size
+  Bq, Bg = (Bp, Bv) if direction == 'p2v' else (Bv, Bp)
+  off, idx = positives_csr(positives, Bq, Bg)
+  oc = np.zeros(Bv + 1, dtype=np.int32)
+  op = np.zeros(Bp + 1, dtype=np.int32)
+  np.cumsum(nclips, out=oc[1:])
+  np.cumsum(ncaps, out=op[1:])
+  cap = _lib.group_rank_labelled_plan_max(Bv, Bp, idx.size)
+  if cap > 0x7fffffff:
+    raise ValueError('%d groups and %d (query, positive) pairs: the plan does not fit int32' % (Bv + Bp, idx.size))
+  plan = np.empty(cap, dtype=np.int32)
+  n = _lib.load().cmhse_group_rank_labelled_plan(oc.ctypes.data, Bv, op.ctypes.data, Bp, _GROUP_DIRECTION[direction],
+                                                 off.ctypes.data, idx.ctypes.data, idx.size, plan.ctypes.data,
+                                                 plan.size)
+  _lib.check(min(n, 0), 'cmhse_group_rank_labelled_plan')
+  return plan[:n]
+
+
+def group_rank_labelled(clips, caps, num_clips, num_caps, positives, direction='p2v', reduce='max',
+                        return_score=False):
+  """Ranks of every query group against any set of correct gallery groups, by group_scores' block score
+  (cmhse_group_rank_labelled): direction 'p2v' takes every paragraph of caps / num_caps as a query against
+  the videos of clips / num_clips, 'v2p' the reverse; the two sets are independent.  `positives`:
+  positives_csr's forms, the gallery groups that count as correct for each query group.  Returns int32
+  device tensors (rank, top1, best_pos) on the current stream: rank[q] counts the gallery groups that score
+  above query q's best positive (0 = a positive comes first; a negative that ties it exactly is not
+  counted), top1 is the best gallery group (the smaller index on exact ties), best_pos that best positive
+  (the smallest index on exact ties); with return_score also its float32 block score, bit-identical to the
+  same entry of group_scores.  Exact fp32 whatever math_mode() says; neither the clip x caption nor the
+  query x gallery matrix is stored."""
+  if reduce not in _GROUP_REDUCE:
+    raise ValueError("reduce must be 'max' or 'mean', got %r" % (reduce,))
+  if direction not in _GROUP_DIRECTION:
+    raise ValueError("direction must be 'p2v' or 'v2p', got %r" % (direction,))
+  for t, name in ((clips, 'clips'), (caps, 'caps')):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+      raise ValueError('%s must be a 2-D tensor' % name)
+  if clips.shape[1] != caps.shape[1]:
+    raise ValueError('embedding widths differ')
+  plan = group_rank_labelled_plan(num_clips, num_caps, clips.shape[0], caps.shape[0], positives, direction)
+  lib = _lib.load()
+  c = _f32c(clips, 'clips')
+  s = _f32c(caps, 'caps')
+  Bq = int(plan[1] if direction == 'p2v' else plan[0])
+  out = torch.empty(3, Bq, dtype=torch.int32, device=c.device)
+  score = torch.empty(Bq, dtype=torch.float32, device=c.device) if return_score else None
+  ws_bytes = lib.cmhse_group_rank_labelled_workspace(plan.ctypes.data, plan.size)
+  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=c.device)
+  plan_d = upload(plan, c.device)
+  rc = lib.cmhse_group_rank_labelled(c.data_ptr(), s.data_ptr(), c.shape[0], s.shape[0], c.shape[1],
+                                     plan.ctypes.data, plan_d.data_ptr(), plan.size, _GROUP_DIRECTION[direction],
+                                     _GROUP_REDUCE[reduce], out[0].data_ptr(), out[1].data_ptr(),
+                                     out[2].data_ptr(), score.data_ptr() if return_score else None,
+                                     ws.data_ptr(), ws_bytes, _stream())
+  _lib.check(rc, 'cmhse_group_rank_labelled')
+  return (out[0], out[1], out[2], score) if return_score else (out[0], out[1], out[2])
+
+
 def cosine_sim(im, s):
   """loss.cosine_sim on device: im @ s.T, exact fp32 (cmhse_cosine_sim)."""
   lib = _lib.load()

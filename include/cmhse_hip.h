@@ -725,6 +725,78 @@ int cmhse_group_topk_exact(const float* clips, const float* caps, int32_t Nc, in
                            int32_t reduce, int32_t K, double* scores /*[Bq,K]*/, int32_t* index /*[Bq,K]*/,
                            int32_t* resolved /*[Bq]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Labelled group-wise ranking (no reference counterpart): cmhse_sim_rank_labelled's protocol on the block
+ * score above — any video set against any paragraph set (Bv videos of clips [Nc, D], Bp paragraphs of caps
+ * [Ns, D]: Bv and Bp independent, every count 1..CMHSE_GROUP_TILE_ROWS rows), any set of correct gallery groups
+ * per query group, matrix-free.
+ *   CMHSE_GROUP_P2V  every paragraph is a query, the videos are the gallery (Bq = Bp, Bg = Bv);
+ *   CMHSE_GROUP_V2P  every video is a query, the paragraphs are the gallery (Bq = Bv, Bg = Bp).
+ * G(q, g) is the block score of cmhse_group_scores / cmhse_group_topk, bit for bit, in both reduce modes: always
+ * the clips x captions tile, reduced clip-major then caption, with the fp64 sum for the mean, whichever side is
+ * the query.  Every query group q has a non-empty list P_q of gallery groups in [0, Bg) (duplicates inside a list
+ * are harmless).  With thr[q] = max over p in P_q of G(q, p), all outputs [Bq]:
+ *   rank[q]       = #{ g in [0, Bg) : G(q, g) > thr[q] }   the 0-based position of the best-placed positive.
+ *                   Strict, no gallery group excluded: no positive beats thr[q], and a negative that ties it
+ *                   exactly is not counted (the optimistic tie rule of cmhse_sim_rank_labelled);
+ *   top1[q]       = argmax_g G(q, g), the smaller g on exact ties (the 64-bit score key of cmhse_group_topk);
+ *   best_pos[q]   = the p in P_q with G(q, p) == thr[q], the smallest such p on exact ties;
+ *   best_score[q] = the bits of G(q, best_pos[q]) as the kernel computed them, never recomputed (may be NULL).
+ * Properties:
+ *   - Square case: with Bv == Bp and P_q = {q}, rank and top1 equal cmhse_group_rank's for that direction, bit
+ *     for bit (its rank excludes the diagonal, which never beats itself).
+ *   - Stripes: a query subset is a smaller call with its rows, counts and labels sliced; the results of query
+ *     stripes concatenate bit for bit into the whole call's.
+ *   - The result depends on neither tiling, panel count, scheduling nor math mode: counts and 64-bit keys are
+ *     integers, and the thresholds come out of the same MFMA chain and the same block reduction as the scores
+ *     they are compared with, which is what makes the strict compare exact.  No float atomics anywhere.
+ *   - Workspace: one 8-byte key per query group, and per gallery panel one 4-byte count and one 8-byte key per
+ *     query group: O(panels x Bq) + O(Bq).  It never holds Bq x Bg or Nc x Ns values; the panel count follows
+ *     cmhse_group_topk's rule (it fills the CUs once), so past that count the workspace does not grow with the
+ *     gallery.  At Bv = Bp = 4917 (val_1): under 1 MB, against cmhse_group_rank's 106 MB.
+ *   - No device memory is written from host memory inside the call: everything the kernels read — offsets,
+ *     tiles, labels, pair tiles — arrives in the plan the caller uploads.
+ *
+ * cmhse_group_rank_labelled_plan (host only, no GPU needed): from the host prefix sums clip_off_host[Bv+1] and
+ * cap_off_host[Bp+1] (0 first, strictly increasing) and the labels as CSR over the query groups —
+ * pos_off_host[Bq+1] (0 first, strictly increasing: every query has a positive; pos_off_host[Bq] == n_pairs)
+ * and pos_idx_host[n_pairs]; query q owns pos_idx_host[pos_off_host[q] .. pos_off_host[q+1]) — fills
+ * plan[0, len) and returns len, or
+ *   CMHSE_ERR_ARG          a null pointer; Bv or Bp <= 0; a bad direction; bad prefix sums; pos_off_host[0] != 0,
+ *                          an empty list, pos_off_host[Bq] != n_pairs; an index outside [0, Bg);
+ *   CMHSE_ERR_UNSUPPORTED  a video or paragraph of more than 128 rows (or a plan beyond int32);
+ *   CMHSE_ERR_WORKSPACE    plan_cap < CMHSE_GROUP_RANK_LABELLED_PLAN_MAX(Bv, Bp, n_pairs).
+ * The labels are validated in full here (O(n_pairs)).  Layout (int32): Bv, Bp, Nc, Ns, direction, R clip tiles,
+ * C caption tiles, n_pairs, T pair tiles, the query cap; clip_off[Bv+1], cap_off[Bp+1], the first video of each
+ * clip tile [R+1], the first paragraph of each caption tile [C+1], pos_off[Bq+1], pos_idx[n_pairs], the first
+ * pair of each pair tile [T+1].  The gallery side packs as cmhse_group_plan does (whole groups, <= 128 rows a
+ * tile); the query side also caps the groups of a tile at 72 (the LDS a query group takes here: no K lists, so
+ * the cap lies above cmhse_group_topk_plan's).  Pair tiles: the (query, positive) pairs in CSR order, whole
+ * pairs packed greedily while the clip rows and the caption rows of a tile both stay <= 128 (a query with many
+ * or long positives spans several tiles).  The caller uploads plan[0, len) and passes both copies: the host
+ * copy is validated in full (O(Bv + Bp + n_pairs)) and sizes the launches, the kernels read the device copy,
+ * which must hold the same values.  The direction is recorded in the plan and must equal the call's.
+ * cmhse_group_rank_labelled_workspace: bytes for the plan (0 for an invalid plan), 256-byte aligned.
+ *
+ * cmhse_group_rank_labelled returns, before anything is launched: CMHSE_ERR_ARG for a null pointer (best_score
+ * excepted); Nc, Ns or D <= 0; a bad reduce or direction; a plan that fails the check above or disagrees with
+ * the call (Nc, Ns, direction, its length); then CMHSE_ERR_WORKSPACE for a workspace that is unaligned (256
+ * bytes) or smaller than cmhse_group_rank_labelled_workspace.
+ * Cost: a threshold pass of T tiles of 128 x 128 x D (operand rows gathered by address; each tile's diagonal
+ * blocks folded into their queries' keys by a 64-bit atomic max), the counting pass — cmhse_group_topk's grid of
+ * query tiles x gallery panels, i.e. the tile work of cmhse_group_scores once — and one small launch.  Inputs
+ * are assumed finite.  Exact fp32 whatever the math mode. */
+#define CMHSE_GROUP_RANK_LABELLED_PLAN_MAX(Bv, Bp, n_pairs) (3 * (Bv) + 3 * (Bp) + 2 * (n_pairs) + 16)
+int32_t cmhse_group_rank_labelled_plan(const int32_t* clip_off_host, int32_t Bv, const int32_t* cap_off_host,
+                                       int32_t Bp, int32_t direction, const int32_t* pos_off_host,
+                                       const int32_t* pos_idx_host, int32_t n_pairs, int32_t* plan,
+                                       int32_t plan_cap);
+size_t cmhse_group_rank_labelled_workspace(const int32_t* plan_host, int32_t plan_len);
+int cmhse_group_rank_labelled(const float* clips, const float* caps, int32_t Nc, int32_t Ns, int32_t D,
+                              const int32_t* plan_host, const int32_t* plan, int32_t plan_len, int32_t direction,
+                              int32_t reduce, int32_t* rank /*[Bq]*/, int32_t* top1 /*[Bq]*/,
+                              int32_t* best_pos /*[Bq]*/, float* best_score /*[Bq] or NULL*/, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* Replaces loss.cosine_sim (loss.py:12-13): scores[n,m] = im s^T, exact fp32. */
 int cmhse_cosine_sim(const float* im, const float* s, int32_t n, int32_t m, int32_t D,
                      float* scores, void* stream);
